@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Salience-DETR encoder hot path on MI355X (contract: see task / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 One "step" = one pass of the hot path (F0 pyramid plumbing -> F1-F3 hierarchical salience filtering ->
 6-layer salience encoder, i.e. reference SalienceTransformer.forward lines 97-183) over ONE batch of
@@ -10,10 +10,12 @@ synthetic 800x1333 4-level pyramids resident in HBM, batch-per-GPU = 2, bf16 enc
 batches with no data-path collective (weak scaling); the timed region is bracketed by
 barrier + synchronize on both sides and the MAX over ranks is reported.
 
-Rank 0 prints ONE JSON line: whole-job images/s, ms per encoder layer, the `roofline` object of the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints whole-job images/s
+and `ms_per_step`; `--dump-outputs DIR` first writes what the last timed step returned (`memory`, the salience
+maps) as float32 .npy files.  `--full` adds everything else: ms per encoder layer, the `roofline` object of the
 dominant kernel (the fused MSDA gather, measured live with stream events around every launch of an
-instrumented pass) and, at N=1, the `cpu_baseline` (the oracle's CPU port of the same path, timed on the
-host cores).
+instrumented pass), batches in flight, the `train_step` and `configs` sub-records and, at N=1, the
+`cpu_baseline` (the oracle's CPU port of the same path, timed on the host cores).
 """
 import argparse
 import json
@@ -35,6 +37,7 @@ DEFAULT_THREADS = torch.get_num_threads()
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 MSDA_REPEATS = 8
 CUT_PAIRS, CUT_REPLAYS = 30, 20   # in-step MSDA timing: paired cut-graph measurements
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: payload of all files together (64 MB less room for the .npy headers)
 
 
 def parse():
@@ -56,12 +59,12 @@ def parse():
                     help="train mode, one process: take the N > 1 execution path anyway (captured forward + backward + "
                          "gradient pack, eager flat all-reduce + optimizer) -- how that path is exercised on a 1-GPU box")
     ap.add_argument("--train-steps", type=int, default=5,
-                    help="the default line's `train_step` sub-record: this many timed training steps (0: skip)")
+                    help="the --full line's `train_step` sub-record: this many timed training steps (0: skip)")
     ap.add_argument("--config-steps", type=int, default=10,
-                    help="the default line's `configs` sub-records (fp32 path, BASELINE configs[3] and configs[4] at N = 1): "
+                    help="the --full line's `configs` sub-records (fp32 path, BASELINE configs[3] and configs[4] at N = 1): "
                          "timed steps each (0: skip)")
     ap.add_argument("--in-flight", dest="in_flight", type=int, default=1,
-                    help="--plain only, informational: this many independent batches (own inputs, own graph, own "
+                    help="without --full only, informational: this many independent batches (own inputs, own graph, own "
                          "stream) replayed side by side; the official line is 1")
     ap.add_argument("--in-flight-report", dest="in_flight_report", type=int, default=3,
                     help="the full line's informational `batches_in_flight` object: this many lanes (0/1: skip)")
@@ -72,13 +75,27 @@ def parse():
                          "(default; 11-bit mantissa, gather via v_fma_mix_f32) or the activation dtype (bf16)")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of a hipGraph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--plain", action="store_true",
-                    help="only the timed loop and a minimal JSON line (what the rocprofv3 counter passes wrap: no "
-                         "instrumented pass, no truncated graphs, no CPU baseline)")
+    depth = ap.add_mutually_exclusive_group()
+    depth.add_argument("--full", action="store_true",
+                       help="after the headline measurement: ms per encoder layer, the MSDA roofline (instrumented pass, "
+                            "cut graphs), batches in flight, the train_step and configs sub-records and the CPU baseline "
+                            "with its parity check")
+    depth.add_argument("--plain", action="store_true",
+                       help="the default without --full: only the timed loop and the headline JSON line (what the "
+                            "rocprofv3 counter passes wrap); kept for the scripts that name it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, a training "
+                         "loss float64; at most %d MiB in all, larger outputs as a fixed seeded sample of their elements)"
+                         % (DUMP_BUDGET_BYTES >> 20))
     ap.add_argument("--cpu-protocol", choices=["bounded", "full"], default="bounded",
-                    help="bounded (default): batch 2, all cores, 1 warm-up + 3 passes; full: SURVEY.md 8(d) -- 3 warm-ups + "
+                    help="--full only: bounded (default): batch 2, all cores, 1 warm-up + 3 passes; full: SURVEY.md 8(d) -- 3 warm-ups + "
                          "10 passes at all cores and at 8 threads, batch 1 and 2 (minutes)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.in_flight > 1:
+        ap.error("--dump-outputs times one batch at a time: drop --in-flight")
+    return args
 
 
 def make_inputs(batch, h, w, device, seed):
@@ -91,6 +108,23 @@ def make_inputs(batch, h, w, device, seed):
     cpu = (feats, masks, pos)
     dev = tuple([t.to(device) for t in ts] for ts in cpu)
     return sizes, canvas, shapes, cpu, dev
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each named tensor as DIR/<name>.npy in float32 (float64 stays float64).  When the outputs
+    together exceed DUMP_BUDGET_BYTES, each is replaced by the same share of its elements, picked by a fixed seed and
+    kept in flat-index order: the same positions on every run, so two builds compare element for element."""
+    import numpy as np
+    arrays = {k: v.detach().cpu() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = a.numel() * DUMP_BUDGET_BYTES // total
+            pick = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.flatten()[pick]
+        np.save(os.path.join(directory, name + ".npy"), a.numpy())
 
 
 def algorithmic_bytes(B, Nv, Nq, M, D, L, P, value_bytes, proj_bytes, out_bytes, ref_dim=2):
@@ -360,6 +394,8 @@ def train_record(args, model, device, rank, world, dist, steps, warmup, force_di
 def train_main(args, model, device, rank, world, dist):
     result = train_record(args, model, device, rank, world, dist, args.steps, args.warmup,
                           force_dist_path=args.force_dist_path)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([result["loss"]], dtype=torch.float64)})
     if rank == 0:
         print(json.dumps(result))
     if dist is not None:
@@ -368,9 +404,9 @@ def train_main(args, model, device, rank, world, dist):
 
 
 def spawn_ranks_if_needed(args):
-    """`python bench.py --gpus N` (N > 1) without a launcher environment re-executes itself under
-    torch.distributed.run with N ranks on this node, so the printed `n_gpus` is always the number of ranks that
-    actually ran (the reference launches its ranks with `accelerate launch`, main.py:94-103,144)."""
+    """`python bench.py --gpus N` (N > 1) without a launcher environment runs itself under torch.distributed.run
+    with N ranks on this node, in a child process, and exits with its status, so the printed `n_gpus` is always the
+    number of ranks that actually ran (the reference launches its ranks with `accelerate launch`, main.py:94-103,144)."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     import socket
@@ -379,7 +415,8 @@ def spawn_ranks_if_needed(args):
         port = sock.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def kernel_source_tag():
@@ -819,7 +856,10 @@ def main():
 
     def step():
         with torch.no_grad():
-            return model(feats, masks, pos, image_sizes=sizes, canvas=canvas)[0]
+            memory, score_maps = model(feats, masks, pos, image_sizes=sizes, canvas=canvas)
+        # the salience maps are held past the step only when they are dumped: otherwise the captured graph's pool
+        # reuses their buffers, as it does for every other intermediate
+        return (memory, score_maps) if args.dump_outputs else (memory,)
 
     for _ in range(max(args.warmup, 3)):
         out = step()
@@ -851,8 +891,8 @@ def main():
         torch.cuda.synchronize()
 
     lanes = []
-    if args.plain and graphed and args.in_flight > 1 and args.dtype == "bf16":
-        lanes = make_lanes(model, args, device, rank, (g, out, step), args.in_flight, capture_kw, sizes, canvas)
+    if not args.full and graphed and args.in_flight > 1 and args.dtype == "bf16":
+        lanes = make_lanes(model, args, device, rank, (g, out[0], step), args.in_flight, capture_kw, sizes, canvas)
         run = lane_runner(lanes)
         for _ in range(2 * len(lanes)):
             run()
@@ -860,7 +900,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
@@ -870,15 +910,35 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     images_per_s = world * args.batch * args.steps / elapsed
 
+    if rank == 0 and args.dump_outputs:
+        memory, score_maps = out if graphed else last   # (a replay refills the captured outputs)
+        dump_outputs(args.dump_outputs, {"memory": memory,
+                                         **{"salience_score_%d" % i: s_ for i, s_ in enumerate(score_maps)}})
+
+    result = {
+        "metric": "images/s (whole node) + ms/encoder-layer, ResNet50 800x1333",
+        "value": round(images_per_s, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
+        "config": {"workload": "salience_detr_resnet50_800_1333 %s inference, batch=%d per MI355X: pyramid flatten + "
+                               "hierarchical salience filtering + 6-layer salience encoder (MSDA)" % (args.dtype, args.batch),
+                   "batch_per_gpu": args.batch, "global_batch": args.batch * world,
+                   "image": [args.height, args.width], "levels": [list(s) for s in level_shapes],
+                   "value_map_storage": ("fp16" if (args.dtype == "bf16" and args.value_dtype == "fp16") else args.dtype),
+                   "parallelism": "replicas, images sharded across GPUs, no data-path collective",
+                   "hipgraph": graphed, "hipgraph_nodes": main_capture.get("graph_nodes"),
+                   "hipgraph_memset_nodes": main_capture.get("memset_nodes"),
+                   "world_size": world, "backend": backend or "none (single process)"},
+    }
+    out = out[0]   # what the --full measurements below compare: `memory`
+
     nl = model.encoder.num_layers
-    if args.plain:
-        lanes_identical = lanes_match_solo(lanes) if lanes else None
+    if not args.full:
+        if lanes:
+            result["batches_in_flight"] = len(lanes)
+            result["lanes_bit_identical_to_solo"] = lanes_match_solo(lanes)
         if rank == 0:
-            print(json.dumps({"metric": "images/s (whole node) + ms/encoder-layer, ResNet50 800x1333",
-                              "value": round(images_per_s, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-                              "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "dtype": args.dtype,
-                              "hipgraph": graphed, "plain": True, "batches_in_flight": max(1, len(lanes)),
-                              "lanes_bit_identical_to_solo": lanes_identical}))
+            print(json.dumps(result))
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
@@ -1140,24 +1200,9 @@ def main():
                        % MSDA_REPEATS,
     }
 
-    result = {
-        "metric": "images/s (whole node) + ms/encoder-layer, ResNet50 800x1333",
-        "value": round(images_per_s, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "salience_detr_resnet50_800_1333 %s inference, batch=%d per MI355X: pyramid flatten + "
-                               "hierarchical salience filtering + 6-layer salience encoder (MSDA)" % (args.dtype, args.batch),
-                   "batch_per_gpu": args.batch, "global_batch": args.batch * world,
-                   "image": [args.height, args.width], "levels": [list(s) for s in level_shapes],
-                   "value_map_storage": ("fp16" if (args.dtype == "bf16" and args.value_dtype == "fp16") else args.dtype),
-                   "parallelism": "replicas, images sharded across GPUs, no data-path collective",
-                   "hipgraph": graphed, "hipgraph_nodes": main_capture.get("graph_nodes"),
-                   "hipgraph_memset_nodes": main_capture.get("memset_nodes"),
-                   "world_size": world, "backend": backend or "none (single process)"},
-        "ms_per_encoder_layer": {"mean": (round(sum(layer_ms) / nl, 4) if layer_ms[0] is not None else None),
-                                 "per_layer": [None if x is None else round(x, 4) for x in layer_ms], "note": layer_note},
-        "roofline": roofline,
-    }
+    result["ms_per_encoder_layer"] = {"mean": (round(sum(layer_ms) / nl, 4) if layer_ms[0] is not None else None),
+                                      "per_layer": [None if x is None else round(x, 4) for x in layer_ms], "note": layer_note}
+    result["roofline"] = roofline
 
     # ---- informational: the same K steps with three independent batches in flight (own inputs, graph, stream) ----
     # One batch is a dependent chain of ~76 launches, most of which fill a fraction of the 256 CUs; a server with

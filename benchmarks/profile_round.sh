@@ -5,14 +5,14 @@
 # Everything lands in gpurun_out/<tag>_*; copy what should be judged into profiles/.
 # Counter passes carry --kernel-trace only (no other trace domain), one --pmc set per pass.
 # (The survey's full CPU-baseline protocol -- minutes of host time -- runs last when FULL_CPU=1:
-# `python bench.py --cpu-protocol full` -> <tag>_bench_cpu_full.json.)
+# `python bench.py --full --cpu-protocol full` -> <tag>_bench_cpu_full.json.)
 set -u
 R=${1:-r06}
 O=$PWD/gpurun_out
 mkdir -p $O profiles
 export TMPDIR=/tmp
 # 1. PMC traffic passes first: the bench line's roofline.traffic is read from profiles/${R}_msda_traffic.json
-python bench.py --no-cpu-baseline --train-steps 0 --in-flight-report 0 --config-steps 0 > $O/${R}_bench_quick.json 2> $O/${R}_bench_quick.err
+python bench.py --full --no-cpu-baseline --train-steps 0 --in-flight-report 0 --config-steps 0 > $O/${R}_bench_quick.json 2> $O/${R}_bench_quick.err
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/${R}_pmc_$c -o p -- \
     python bench.py --plain --no-graph --steps 5 --warmup 3 > /dev/null 2> $O/${R}_pmc_$c.err
@@ -47,7 +47,7 @@ print(open(sys.argv[2]).read())
 PY
 cp $O/${R}_msda_rocprof.json profiles/${R}_msda_rocprof.json
 rm -rf $O/${R}_prof
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/${R}_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/${R}_bench.err
 tail -c 300 $O/${R}_bench.json
 head -8 $O/${R}_bench_kernel_stats.csv | cut -c1-150
 # 3. counters of the fused MSDA forward kernels (layer 0 size: round 3's resident kernel, the bordered kernel without and
@@ -124,6 +124,6 @@ done
   timeout 60 ./benchmarks/micro/gemm_x3_ablate_0 22726 256 2048 fwd 1 | sed 's/}$/, "generation": "128x128 tiles"}/'
   echo ']}' ) > $O/${R}_gemm_x3_ablate.json 2> /dev/null
 if [ "${FULL_CPU:-0}" = "1" ]; then
-  python bench.py --cpu-protocol full --train-steps 0 --in-flight-report 0 --config-steps 0 > $O/${R}_bench_cpu_full.json 2> $O/${R}_bench_cpu_full.err
+  python bench.py --full --cpu-protocol full --train-steps 0 --in-flight-report 0 --config-steps 0 > $O/${R}_bench_cpu_full.json 2> $O/${R}_bench_cpu_full.err
 fi
 ls $O | grep "^${R}" | head -40
