@@ -35,6 +35,7 @@ typedef struct ihipStream_t *sdetr_stream_t; /* == hipStream_t */
 #define SDETR_F32 0
 #define SDETR_BF16 1
 #define SDETR_F16 2 /* IEEE half: the head-major value maps (either library); the activations of the fp16 flavour */
+#define SDETR_I64 3 /* int64 (sdetr_detection_postprocess's target sizes) */
 
 /*
  * Two builds of this ABI (round 5).  The token-resident kernels keep their ACTIVATIONS -- token rows, projection slabs,
@@ -1022,6 +1023,32 @@ int sdetr_sampling_prep_backward_f32(sdetr_stream_t stream, const float *grad_sa
                                      const float *reference_points, const int64_t *spatial_shapes, int64_t rows,
                                      int num_heads, int num_levels, int num_points, int ref_dim, float *grad_offsets,
                                      float *grad_logits);
+
+/* ---- (14) detection post-processing (reference models/bricks/post_process.py:PostProcess) ----------------------------
+ * sdetr_detection_postprocess: what SalienceDETR.forward returns in eval mode (models/detectors/salience_detr.py:241-243),
+ * one launch for the batch (one 1024-thread workgroup per image).  logits [batch, num_queries, num_classes] (f32 or this
+ * library's 16-bit type; images logits_batch_stride elements apart, >= num_queries * num_classes, the rows themselves
+ * contiguous); boxes f32 [batch, num_queries, 4] (cx, cy, w, h), images boxes_batch_stride floats apart;
+ * target_sizes [batch, 2] (h, w), sizes_dtype SDETR_I64 or SDETR_F32.
+ * Selection: the top k of the num_queries * num_classes flattened entries of each image by LOGIT descending, ties to the
+ * lower flat index, -0.0 == +0.0 (one of the orders torch.topk(sigmoid(logits)) may return; deterministic where topk's is
+ * not).  NaN logits: unspecified order, no fault.  Writes per image, in rank order:
+ *   out_scores [batch, k] sigmoid(logit) in fp32 rounded to the logits' type;  out_labels int64 [batch, k] = flat % C;
+ *   out_boxes f32 [batch, k, 4] = the box of query flat / C as (cx - 0.5w, cy - 0.5h, cx + 0.5w, cy + 0.5h) * (w, h, w, h),
+ *   each operation rounded on its own;  out_count int32 [batch] = entries kept by the filters.
+ * Filters (post_process.py:43-64): score_threshold > 0 keeps score > threshold compared in the score's type (the
+ * threshold is rounded to it); iou_threshold > 0 runs greedy class-agnostic NMS (torchvision.ops.nms's rule, fp32 IoU
+ * inter / (area_i + area_j - inter) > iou_threshold) over ALL k boxes in rank order, and an entry is kept if it passes
+ * both -- a box below the confidence threshold can still suppress.  NMS without a confidence threshold is NMS alone (the
+ * reference fails there).  Kept entries are compacted to the front; every slot past out_count is written (score 0,
+ * label -1, box 0): no fill has to precede the launch, and the launch can be captured into a graph.
+ * Bounds: batch >= 1, 1 <= k <= min(num_queries * num_classes, 1024), num_queries * num_classes <= 2^24.  Rows of up to
+ * 40 960 entries are read from memory once; longer rows are streamed once per select round. */
+int sdetr_detection_postprocess(sdetr_stream_t stream, const void *logits, int logits_dtype, int64_t logits_batch_stride,
+                                const float *boxes, int64_t boxes_batch_stride, const void *target_sizes, int sizes_dtype,
+                                int batch, int num_queries, int num_classes, int k, float score_threshold,
+                                float iou_threshold, void *out_scores, int64_t *out_labels, float *out_boxes,
+                                int *out_count);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense multi-head attention over a few hundred rows for the TRAINING step, fp32, 32-channel heads

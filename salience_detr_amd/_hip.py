@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libsalience_hip.so")
 # operator picks the library by the dtype of the activations it is handed: ``lib(x.dtype)``.
 F16_LIB_PATH = os.path.join(_HERE, "libsalience_hip_f16.so")
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16, I64 = 0, 1, 2, 3
 EINVAL = -1
 ACT16 = (torch.bfloat16, torch.float16)      # the two 16-bit activation types (one library each)
 
@@ -198,6 +198,8 @@ SIGNATURES = {
     "sdetr_neck_combine": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _i]),
     "sdetr_neck_gate_workspace_bytes": (_i64, [_i, _i, _i]),
     "sdetr_neck_gate_shortcut": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i64, _p, _p]),
+    "sdetr_detection_postprocess": (_i, [_p, _p, _i, _i64, _p, _i64, _p, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                         _p, _p, _p, _p]),
 }
 
 
