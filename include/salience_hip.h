@@ -1050,6 +1050,76 @@ int sdetr_detection_postprocess(sdetr_stream_t stream, const void *logits, int l
                                 float iou_threshold, void *out_scores, int64_t *out_labels, float *out_boxes,
                                 int *out_count);
 
+/* ---- (15) the set criterion (reference models/bricks/set_criterion.py:HybridSetCriterion with
+ *      models/matcher/hungarian_matcher.py:HungarianMatcher, models/bricks/losses.py:15-22) -------------------------------
+ * One decoder / encoder output of the loss: logits [batch, num_queries, num_classes] (f32 or this library's 16-bit type,
+ * the same type for every output of a call; rows contiguous, images logits_batch_stride elements apart, >= num_queries *
+ * num_classes when batch > 1 -- a [:, :pad] query slice of a larger tensor qualifies); boxes f32 [batch, num_queries, 4]
+ * (cx, cy, w, h), 16-byte aligned, images boxes_batch_stride floats apart (a multiple of 4); binary_cls != 0 reads every
+ * target label as 0 (set_criterion.py:161-166, the encoder output with two_stage_binary_cls).  At most 16 per call.
+ * Targets, staged once per batch: tgt_boxes f32 [sum T, 4] (cx, cy, w, h, 16-byte aligned), tgt_labels int32 [sum T],
+ * tgt_offsets int32 [batch + 1] (image b owns rows [offsets[b], offsets[b+1])), all on the device; t_cap = a host-side
+ * bound on any image's target count.  Problem p = output * batch + image. */
+typedef struct sdetr_set_output {
+    const void *logits;
+    int64_t logits_batch_stride;
+    const float *boxes;
+    int64_t boxes_batch_stride;
+    int binary_cls;
+} sdetr_set_output;
+
+/* bytes of the cost buffer sdetr_set_match needs: problems * t_cap * num_queries floats */
+int64_t sdetr_set_match_workspace_bytes(int problems, int t_cap, int num_queries);
+
+/* sdetr_set_match: the matcher of every (output, image) problem of a step in two launches.
+ * Cost (hungarian_matcher.py:41-71), fp32: cost_class * (pos - neg)[label] with neg = -(1 - alpha) p^gamma log(1 - p + 1e-6),
+ * pos = -alpha (1 - p)^gamma log(p + 1e-6), p = sigmoid(logit); + cost_bbox * L1 distance of the cxcywh boxes
+ * + cost_giou * (-GIoU) of the xyxy boxes; written target-major to workspace as f32 [problem, t_cap, num_queries] (rows
+ * t >= T of an image are not written).  Assignment: an exact minimum-cost assignment of each image's T targets to distinct
+ * queries (shortest augmenting paths, fp64 duals: optimal for the fp32 cost up to fp64 rounding; ties between optimal
+ * assignments may resolve differently from scipy).  Writes match int32 [problem, num_queries] = target index or -1;
+ * duals (nullable) f64 [problem, num_queries + t_cap] = the column duals v then the row duals u (0 past T): c - u - v >= 0
+ * everywhere, == 0 on matched pairs, v == 0 on unmatched columns; status (nullable) int32 [problem] = 0, or 1 (T >
+ * num_queries), 2 (T > t_cap), 3 (no finite assignment: NaN / inf cost), the match row then all -1.
+ * Denoising mode (dn_groups > 0; base_detector.py:205-218): no cost, no logits / boxes / labels read (outputs may be null):
+ * match[p, g * dn_max_gt + t] = t for g < dn_groups, t < min(T, dn_max_gt), -1 elsewhere; status 2 where T > dn_max_gt.
+ * Bounds: t_cap <= num_queries, t_cap <= 65535, 25 * num_queries + 13 * t_cap <= 65536 (LDS of the one-wavefront
+ * assignment: num_queries up to 1724 at t_cap = num_queries); dn_groups * dn_max_gt <= num_queries. */
+int sdetr_set_match(sdetr_stream_t stream, const sdetr_set_output *outputs, int n_outputs, int logits_dtype, int batch,
+                    int num_queries, int num_classes, const float *tgt_boxes, const int *tgt_labels, const int *tgt_offsets,
+                    int t_cap, float cost_class, float cost_bbox, float cost_giou, float focal_alpha, float focal_gamma,
+                    int dn_groups, int dn_max_gt, void *workspace, int64_t workspace_bytes, int *match, double *duals,
+                    int *status);
+
+/* bytes of the partial sums sdetr_set_loss needs (f64, [n_outputs, batch, ceil(Nq * C / 2048), 3]) */
+int64_t sdetr_set_loss_workspace_bytes(int n_outputs, int batch, int num_queries, int num_classes);
+
+/* sdetr_set_loss: the unweighted losses of every output given its match [n_outputs * batch, num_queries] (what
+ * sdetr_set_match wrote, or any per-image assignment of distinct queries): losses f32 [n_outputs, 3] =
+ *   loss_class  sum over all logits of BCE-with-logits(x, s) * ((1 - alpha) p^gamma (1 - onehot) + s), p = sigmoid(x),
+ *               s = onehot * IoU(matched query box, its target box) (vari_sigmoid_focal_loss, set_criterion.py:179-199);
+ *   loss_bbox   sum over matched pairs of |box - target|_1;   loss_giou   sum over matched pairs of 1 - GIoU;
+ * each divided by num_boxes * num_boxes_scale, num_boxes = *num_boxes (a device scalar, e.g. the all-reduced count) or,
+ * when null, max(tgt_offsets[batch], 1).  Two launches: per-block f64 partial sums, then a fixed-order sum per output
+ * (the result does not depend on scheduling). */
+int sdetr_set_loss(sdetr_stream_t stream, const sdetr_set_output *outputs, int n_outputs, int logits_dtype, int batch,
+                   int num_queries, int num_classes, const float *tgt_boxes, const int *tgt_labels, const int *tgt_offsets,
+                   const int *match, const float *num_boxes, float num_boxes_scale, float alpha, float gamma,
+                   void *workspace, int64_t workspace_bytes, float *losses);
+
+/* sdetr_set_loss_backward: one launch; grad_losses f32 [n_outputs, 3] (device) = the upstream gradients of losses.
+ * Writes, per output, grad_logits[o] [batch, num_queries, num_classes] contiguous in the logits' type = weight * (p - s) *
+ * g_class / num_boxes (weight and s detached, as the reference), and grad_boxes[o] f32 [batch, num_queries, 4] contiguous
+ * (16-byte aligned) = sign(box - target) * g_bbox / num_boxes (0 on equality) + the GIoU gradient through the cxcywh ->
+ * xyxy conversion (torchvision's formula: clamp(min=0) passes where its input >= 0, min / max split a tie in half) times
+ * -g_giou / num_boxes; 0 on unmatched queries.  Every element is written.  grad_logits / grad_boxes: host arrays of
+ * n_outputs device pointers. */
+int sdetr_set_loss_backward(sdetr_stream_t stream, const sdetr_set_output *outputs, int n_outputs, int logits_dtype,
+                            int batch, int num_queries, int num_classes, const float *tgt_boxes, const int *tgt_labels,
+                            const int *tgt_offsets, const int *match, const float *num_boxes, float num_boxes_scale,
+                            float alpha, float gamma, const float *grad_losses, void *const *grad_logits,
+                            float *const *grad_boxes);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense multi-head attention over a few hundred rows for the TRAINING step, fp32, 32-channel heads
  * (models/bricks/salience_transformer.py:371-376: the encoder layer's self-attention over its top-300 rows, between the

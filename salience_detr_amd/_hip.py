@@ -59,6 +59,12 @@ class RankJobStruct(ctypes.Structure):
                 ("fill_value", ctypes.c_void_p), ("batch", ctypes.c_int), ("n", ctypes.c_int), ("k", ctypes.c_int),
                 ("index_offset", ctypes.c_int64), ("out_score", ctypes.c_void_p), ("out_index", ctypes.c_void_p),
                 ("out_row_stride", ctypes.c_int64)]
+
+
+class SetOutputStruct(ctypes.Structure):
+    """``sdetr_set_output`` of include/salience_hip.h."""
+    _fields_ = [("logits", ctypes.c_void_p), ("logits_batch_stride", ctypes.c_int64), ("boxes", ctypes.c_void_p),
+                ("boxes_batch_stride", ctypes.c_int64), ("binary_cls", ctypes.c_int)]
 _i64 = ctypes.c_int64
 _p = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -200,6 +206,11 @@ SIGNATURES = {
     "sdetr_neck_gate_shortcut": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i64, _p, _p]),
     "sdetr_detection_postprocess": (_i, [_p, _p, _i, _i64, _p, _i64, _p, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                          _p, _p, _p, _p]),
+    "sdetr_set_match_workspace_bytes": (_i64, [_i, _i, _i]),
+    "sdetr_set_match": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i] + [ctypes.c_float] * 5 + [_i, _i, _p, _i64, _p, _p, _p]),
+    "sdetr_set_loss_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "sdetr_set_loss": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p] + [ctypes.c_float] * 3 + [_p, _i64, _p]),
+    "sdetr_set_loss_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p] + [ctypes.c_float] * 3 + [_p, _p, _p]),
 }
 
 
