@@ -19,6 +19,8 @@ from typing import Iterable, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .derived import invalidate_caches
+
 
 def shard_range(num_items: int, rank: int, world_size: int) -> Tuple[int, int]:
     """Contiguous ``[start, stop)`` slice of ``num_items`` independent images for ``rank`` (sizes differ by
@@ -31,9 +33,11 @@ def shard_range(num_items: int, rank: int, world_size: int) -> Tuple[int, int]:
 
 
 def broadcast_parameters(module: torch.nn.Module, src: int = 0, group=None) -> None:
-    """Make every replica start from rank ``src``'s parameters and buffers."""
+    """Make every replica start from rank ``src``'s parameters and buffers (and drop the operands derived from the
+    old values: a write through ``.data`` leaves their keys unchanged)."""
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src=src, group=group)
+    invalidate_caches(module)
 
 
 class FlatGradAllReducer:

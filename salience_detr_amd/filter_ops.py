@@ -8,6 +8,7 @@ import torch
 from torch import Tensor
 
 from . import _hip
+from .derived import derived
 
 
 def masked_topk_desc(score: Tensor, k: int, mask: Optional[Tensor] = None, fill_with_global_min: bool = False,
@@ -456,26 +457,22 @@ def packed_linear_weight(weight: Tensor, cols=None, split3: bool = False) -> Ten
     w = weight.detach()
     if not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or w.stride(1) != 1:
         raise RuntimeError("packed_linear_weight: fp32 [out,in] HIP tensor with a contiguous last dim expected")
-    cache = weight.__dict__.setdefault("_sdetr_packed", {})
-    tag = (weight.data_ptr(), weight._version, str(weight.device), tuple(weight.shape))
-    key = (cols, split3)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit[1]
     if cols is not None:
         w = w[:, cols[0]:cols[1]]
-    with torch.cuda.device(w.device):
-        if split3:
-            out = torch.empty(w.shape[0] * w.shape[1] * 3, dtype=torch.bfloat16, device=w.device)
-            code = _hip.lib().sdetr_pack_linear_bf16x3(_hip.stream_ptr(), w.data_ptr(), w.stride(0), w.shape[0],
-                                                       w.shape[1], out.data_ptr())
-        else:
-            out = torch.empty(w.shape[0] * w.shape[1], dtype=torch.float32, device=w.device)
-            code = _hip.lib().sdetr_pack_linear_f32(_hip.stream_ptr(), w.data_ptr(), w.stride(0), w.shape[0],
-                                                    w.shape[1], out.data_ptr())
-    _hip.check(code, "pack_linear")
-    cache[key] = (tag, out)
-    return out
+
+    def build():
+        with torch.cuda.device(w.device):
+            if split3:
+                out = torch.empty(w.shape[0] * w.shape[1] * 3, dtype=torch.bfloat16, device=w.device)
+                code = _hip.lib().sdetr_pack_linear_bf16x3(_hip.stream_ptr(), w.data_ptr(), w.stride(0), w.shape[0],
+                                                           w.shape[1], out.data_ptr())
+            else:
+                out = torch.empty(w.shape[0] * w.shape[1], dtype=torch.float32, device=w.device)
+                code = _hip.lib().sdetr_pack_linear_f32(_hip.stream_ptr(), w.data_ptr(), w.stride(0), w.shape[0],
+                                                        w.shape[1], out.data_ptr())
+        _hip.check(code, "pack_linear")
+        return out
+    return derived(weight, "packed_linear_x3" if split3 else "packed_linear", (weight,), build, extra=cols)
 
 
 class ValueProjectionJob:
@@ -575,15 +572,13 @@ def _layer1_constant(predictor) -> Tensor:
     """``c0 = layer1.Linear.weight @ layer1.LayerNorm.bias + layer1.Linear.bias`` (fp32 [256]), cached on the weight and
     refreshed when any of the three parameters changes."""
     l1n, l1 = predictor.layer1[0], predictor.layer1[1]
-    tag = tuple((t.data_ptr(), t._version) for t in (l1.weight, l1.bias, l1n.bias)) + (str(l1.weight.device),)
-    hit = l1.weight.__dict__.get("_sdetr_c0")
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    with torch.no_grad():
-        # (elementwise product + a sum per row: no library GEMV -- its accumulation order varies with the handle's state)
-        c0 = ((l1.weight.detach().double() * l1n.bias.detach().double()).sum(1) + l1.bias.detach().double()).float().contiguous()
-    l1.weight.__dict__["_sdetr_c0"] = (tag, c0)
-    return c0
+
+    def build():
+        with torch.no_grad():
+            # (elementwise product + a sum per row: no library GEMV -- its accumulation order varies with the handle's state)
+            return ((l1.weight.detach().double() * l1n.bias.detach().double()).sum(1)
+                    + l1.bias.detach().double()).float().contiguous()
+    return derived(l1.weight, "layer1_constant", (l1.weight, l1.bias, l1n.bias), build)
 
 
 def salience_head_hoist(x: Tensor, predictor, enc_output=None, enc_output_norm=None, memory_out: Optional[Tensor] = None,
@@ -892,24 +887,21 @@ def fused_ffn_applies(x: Tensor, linear1, linear2, norm, activation) -> bool:
             and linear1.out_features <= 8192 and linear1.bias is not None and linear2.bias is not None)
 
 
-def _ffn_operands(x: Tensor, linear1, linear2, norm):
+def _ffn_operands(linear1, linear2, norm):
     """(packed weights, fp32 bias1, bias2, norm weight, norm bias) of the fused feed-forward, cached on
     ``linear1.weight`` and refreshed when any parameter changes."""
-    params = (linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm.weight, norm.bias)
-    tag = tuple((t.data_ptr(), t._version) for t in params) + (str(x.device),)
-    cache = linear1.weight.__dict__.get("_sdetr_ffn")
-    lib = _hip.lib(linear1.weight.dtype)
-    F = linear1.out_features
-    if cache is None or cache[0] != tag:
-        with torch.no_grad(), torch.cuda.device(x.device):
-            packed = torch.empty(lib.sdetr_ffn_packed_bytes(F), dtype=torch.uint8, device=x.device)
+    def build():
+        lib = _hip.lib(linear1.weight.dtype)
+        F, dev = linear1.out_features, linear1.weight.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            packed = torch.empty(lib.sdetr_ffn_packed_bytes(F), dtype=torch.uint8, device=dev)
             w1, w2 = linear1.weight.detach().contiguous(), linear2.weight.detach().contiguous()
             code = lib.sdetr_ffn_pack_bf16(_hip.stream_ptr(), w1.data_ptr(), w2.data_ptr(), 256, F, packed.data_ptr())
             _hip.check(code, "ffn_pack")
             small = [t.detach().float().contiguous() for t in (linear1.bias, linear2.bias, norm.weight, norm.bias)]
-        cache = (tag, packed, small)
-        linear1.weight.__dict__["_sdetr_ffn"] = cache
-    return cache[1], cache[2]
+        return packed, small
+    return derived(linear1.weight, "ffn", (linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm.weight,
+                                           norm.bias), build)
 
 
 def fused_ffn(x: Tensor, linear1, linear2, norm, hidden_splits: Optional[int] = None) -> Tensor:
@@ -921,7 +913,7 @@ def fused_ffn(x: Tensor, linear1, linear2, norm, hidden_splits: Optional[int] = 
         raise RuntimeError("fused_ffn: HIP device tensors required; there is no CPU fallback")
     lib = _hip.lib(x.dtype)
     F = linear1.out_features
-    packed, (b1, b2, g, be) = _ffn_operands(x, linear1, linear2, norm)
+    packed, (b1, b2, g, be) = _ffn_operands(linear1, linear2, norm)
     x2 = x.reshape(-1, 256)
     if not x2.is_contiguous():
         x2 = x2.contiguous()
@@ -957,7 +949,7 @@ def fused_ffn_advance(x: Tensor, linear1, linear2, norm, sorted_result: Tensor, 
         raise RuntimeError("fused_ffn_advance: count must be int64 [B]")
     lib = _hip.lib(x.dtype)
     F = linear1.out_features
-    packed, (b1, b2, g, be) = _ffn_operands(x, linear1, linear2, norm)
+    packed, (b1, b2, g, be) = _ffn_operands(linear1, linear2, norm)
     nxt = torch.empty((B, next_rows, C), dtype=x.dtype, device=x.device) if next_rows > 0 else None
     with torch.cuda.device(x.device):
         splits = int(hidden_splits) if hidden_splits else lib.sdetr_ffn_auto_splits(B * rows, F)
@@ -982,22 +974,22 @@ def attn_tail_ffn_applies(sampled: Tensor, residual: Tensor, output_proj, norm1,
             and norm1.normalized_shape == (256,))
 
 
-def _tail_ffn_operands(x: Tensor, output_proj, norm1, linear1, linear2, norm2, class_head=None):
+def _tail_ffn_operands(output_proj, norm1, linear1, linear2, norm2, class_head=None):
     """``(packed [Wo tail | feed-forward | class head], fp32 (bo, gamma1, beta1, b1, b2, gamma2, beta2, class bias padded
-    to 96 with -inf))``, cached on ``output_proj.weight`` and refreshed when any of the parameters changes."""
+    to 96 with -inf))``, cached on ``output_proj.weight`` (one entry with, one without the class head) and refreshed when
+    any of the parameters changes."""
     params = (output_proj.weight, output_proj.bias, norm1.weight, norm1.bias, linear1.weight, linear1.bias, linear2.weight,
               linear2.bias, norm2.weight, norm2.bias)
     if class_head is not None:
         params = params + (class_head.weight, class_head.bias)
-    tag = tuple((t.data_ptr(), t._version) for t in params) + (str(x.device),)
-    cache = output_proj.weight.__dict__.get("_sdetr_tail_ffn")
-    if cache is None or cache[0] != tag:
+
+    def build():
         lib = _hip.lib(output_proj.weight.dtype)
-        F = linear1.out_features
-        with torch.no_grad(), torch.cuda.device(x.device):
+        F, dev = linear1.out_features, output_proj.weight.device
+        with torch.no_grad(), torch.cuda.device(dev):
             tail_bytes, ffn_bytes = lib.sdetr_attn_tail_packed_bytes(), lib.sdetr_ffn_packed_bytes(F)
             cls_bytes = lib.sdetr_class_head_packed_bytes() if class_head is not None else 0
-            packed = torch.empty(tail_bytes + ffn_bytes + cls_bytes, dtype=torch.uint8, device=x.device)
+            packed = torch.empty(tail_bytes + ffn_bytes + cls_bytes, dtype=torch.uint8, device=dev)
             wo = output_proj.weight.detach().contiguous()
             _hip.check(lib.sdetr_attn_tail_pack_bf16(_hip.stream_ptr(), wo.data_ptr(), 256, packed.data_ptr()), "attn_tail_pack")
             w1, w2 = linear1.weight.detach().contiguous(), linear2.weight.detach().contiguous()
@@ -1009,12 +1001,11 @@ def _tail_ffn_operands(x: Tensor, output_proj, norm1, linear1, linear2, norm2, c
                 wc = class_head.weight.detach().contiguous()
                 _hip.check(lib.sdetr_class_head_pack_bf16(_hip.stream_ptr(), wc.data_ptr(), wc.shape[0], 256,
                                                           packed.data_ptr() + tail_bytes + ffn_bytes), "class_head_pack")
-                cb = torch.full((96,), float("-inf"), dtype=torch.float32, device=x.device)
+                cb = torch.full((96,), float("-inf"), dtype=torch.float32, device=dev)
                 cb[:wc.shape[0]] = class_head.bias.detach().float()
                 small.append(cb)
-        cache = (tag, packed, small)
-        output_proj.weight.__dict__["_sdetr_tail_ffn"] = cache
-    return cache[1], cache[2]
+        return packed, small
+    return derived(output_proj.weight, "tail_ffn" if class_head is None else "tail_ffn_cls", params, build)
 
 
 # The second pass of a split hidden dimension computes the next layer's class score (csrc/ffn.hip,
@@ -1058,7 +1049,7 @@ def attn_tail_ffn_advance(sampled: Tensor, residual: Tensor, output_proj, norm1,
     if with_score and (foreground.dtype != torch.float32 or foreground.dim() != 2 or foreground.shape[0] != B
                        or foreground.shape[1] < next_rows or foreground.stride(1) != 1):
         raise RuntimeError("attn_tail_ffn_advance: foreground must be fp32 [B, >= next_rows] rows")
-    ops = _tail_ffn_operands(residual, output_proj, norm1, linear1, linear2, norm2, next_class_head if with_score else None)
+    ops = _tail_ffn_operands(output_proj, norm1, linear1, linear2, norm2, next_class_head if with_score else None)
     packed, (bo, g1, be1, b1, b2, g2, be2) = ops[0], ops[1][:7]
     cls_bias = ops[1][7] if with_score else None
     nxt = torch.empty((B, next_rows, C), dtype=residual.dtype, device=residual.device) if next_rows > 0 else None
@@ -1080,24 +1071,20 @@ def attn_tail_ffn_advance(sampled: Tensor, residual: Tensor, output_proj, norm1,
 def _packed_linear_bf16(weight: Tensor, bias: Optional[Tensor]):
     """(packed weight, zero-padded fp32 bias) of a ``[N,256]`` bf16 Linear for the token-resident kernels, cached on
     the weight tensor object and refreshed when weight / bias storage or version change."""
-    tag = (weight.data_ptr(), weight._version, None if bias is None else (bias.data_ptr(), bias._version),
-           str(weight.device), tuple(weight.shape))
-    hit = weight.__dict__.get("_sdetr_tl")
-    if hit is not None and hit[0] == tag:
-        return hit[1], hit[2]
-    lib = _hip.lib(weight.dtype)
-    w = weight.detach()
-    N = w.shape[0]
-    npad = (N + 127) // 128 * 128
-    with torch.no_grad(), torch.cuda.device(w.device):
-        packed = torch.empty(lib.sdetr_linear_packed_bytes(N), dtype=torch.uint8, device=w.device)
-        code = lib.sdetr_linear_pack_bf16(_hip.stream_ptr(), w.data_ptr(), w.stride(0), N, w.shape[1], packed.data_ptr())
-        _hip.check(code, "linear_pack")
-        b = torch.zeros(npad, dtype=torch.float32, device=w.device)
-        if bias is not None:
-            b[:N] = bias.detach().float()
-    weight.__dict__["_sdetr_tl"] = (tag, packed, b)
-    return packed, b
+    def build():
+        lib = _hip.lib(weight.dtype)
+        w = weight.detach()
+        N = w.shape[0]
+        npad = (N + 127) // 128 * 128
+        with torch.no_grad(), torch.cuda.device(w.device):
+            packed = torch.empty(lib.sdetr_linear_packed_bytes(N), dtype=torch.uint8, device=w.device)
+            code = lib.sdetr_linear_pack_bf16(_hip.stream_ptr(), w.data_ptr(), w.stride(0), N, w.shape[1], packed.data_ptr())
+            _hip.check(code, "linear_pack")
+            b = torch.zeros(npad, dtype=torch.float32, device=w.device)
+            if bias is not None:
+                b[:N] = bias.detach().float()
+        return packed, b
+    return derived(weight, "token_linear", (weight, bias), build)
 
 
 def _fragment_order(weight: Tensor, rows_per_head: int) -> Tensor:
@@ -1105,16 +1092,12 @@ def _fragment_order(weight: Tensor, rows_per_head: int) -> Tensor:
     16x16x32 products: ``[head][16-row tile][k-step of 32][lane][8]`` with lane = (row & 15) + 16 * (k / 8 & 3) -- a wave's
     operand fragment is one contiguous KB (include/salience_hip.h, sdetr_topk_attention_with_projection_bf16).  Cached on
     the weight object, refreshed when its storage or version changes."""
-    tag = (weight.data_ptr(), weight._version, str(weight.device), tuple(weight.shape))
-    hit = weight.__dict__.get("_sdetr_frag")
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    tiles = rows_per_head // 16
-    with torch.no_grad():
-        # [head, tile c, row t, k-step j, quarter g, element e] -> [head, c, j, g, t, e]
-        frag = weight.detach().view(8, tiles, 16, 8, 4, 8).permute(0, 1, 3, 4, 2, 5).contiguous()
-    weight.__dict__["_sdetr_frag"] = (tag, frag)
-    return frag
+    def build():
+        tiles = rows_per_head // 16
+        with torch.no_grad():
+            # [head, tile c, row t, k-step j, quarter g, element e] -> [head, c, j, g, t, e]
+            return weight.detach().view(8, tiles, 16, 8, 4, 8).permute(0, 1, 3, 4, 2, 5).contiguous()
+    return derived(weight, "fragment_order", (weight,), build, extra=rows_per_head)
 
 
 def token_linear_applies(x: Tensor, weight: Tensor) -> bool:
@@ -1501,12 +1484,8 @@ def rows_linear(x: Tensor, weight: Tensor, bias: Tensor, pos: Optional[Tensor] =
 
 def _norm_f32(norm):
     """fp32 copies of a LayerNorm's weight and bias, cached on the weight tensor (refreshed when the parameters change)."""
-    tag = (norm.weight.data_ptr(), norm.weight._version, norm.bias.data_ptr(), norm.bias._version)
-    hit = norm.weight.__dict__.get("_sdetr_f32")
-    if hit is None or hit[0] != tag:
-        hit = (tag, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-        norm.weight.__dict__["_sdetr_f32"] = hit
-    return hit[1], hit[2]
+    return derived(norm.weight, "norm_f32", (norm.weight, norm.bias),
+                   lambda: (norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()))
 
 
 def decoder_head_applies(query: Tensor, norm, class_head, bbox_layers) -> bool:
@@ -1575,22 +1554,18 @@ def mlp_rows_applies(x: Tensor, layers) -> bool:
 def _packed_linear_512(weight: Tensor, bias: Tensor):
     """(two packed 256-column blocks back to back, fp32 bias) of a ``[256, 512]`` Linear for ``mlp_rows``; cached on the
     weight tensor like ``_packed_linear_bf16``."""
-    tag = (weight.data_ptr(), weight._version, bias.data_ptr(), bias._version, str(weight.device))
-    hit = weight.__dict__.get("_sdetr_tl512")
-    if hit is not None and hit[0] == tag:
-        return hit[1], hit[2]
-    lib = _hip.lib(weight.dtype)
-    w = weight.detach()
-    half = lib.sdetr_linear_packed_bytes(256)
-    with torch.no_grad(), torch.cuda.device(w.device):
-        packed = torch.empty(2 * half, dtype=torch.uint8, device=w.device)
-        for i in range(2):
-            code = lib.sdetr_linear_pack_bf16(_hip.stream_ptr(), w.data_ptr() + i * 256 * w.element_size(), w.stride(0), 256, 256,
-                                              packed.data_ptr() + i * half)
-            _hip.check(code, "linear_pack")
-        b = bias.detach().float().contiguous()
-    weight.__dict__["_sdetr_tl512"] = (tag, packed, b)
-    return packed, b
+    def build():
+        lib = _hip.lib(weight.dtype)
+        w = weight.detach()
+        half = lib.sdetr_linear_packed_bytes(256)
+        with torch.no_grad(), torch.cuda.device(w.device):
+            packed = torch.empty(2 * half, dtype=torch.uint8, device=w.device)
+            for i in range(2):
+                code = lib.sdetr_linear_pack_bf16(_hip.stream_ptr(), w.data_ptr() + i * 256 * w.element_size(), w.stride(0),
+                                                  256, 256, packed.data_ptr() + i * half)
+                _hip.check(code, "linear_pack")
+            return packed, bias.detach().float().contiguous()
+    return derived(weight, "token_linear_512", (weight, bias), build)
 
 
 def mlp_rows(x: Tensor, layers, x_second: Optional[Tensor] = None) -> Tensor:
@@ -1671,20 +1646,18 @@ def _class_head_fragments(class_head):
     """``(packed fragments, fp32 bias padded to 96 with -inf)`` of a ``[<= 96, 256]`` 16-bit class head for the kernels that
     compute ``max_c(class_head(q))`` from an LDS tile (csrc/class_head_core.h); cached on the weight object."""
     w, b = class_head.weight, class_head.bias
-    tag = (w.data_ptr(), w._version, b.data_ptr(), b._version, str(w.device), tuple(w.shape))
-    hit = w.__dict__.get("_sdetr_cls_frag")
-    if hit is not None and hit[0] == tag:
-        return hit[1], hit[2]
-    lib = _hip.lib(w.dtype)
-    with torch.no_grad(), torch.cuda.device(w.device):
-        packed = torch.empty(lib.sdetr_class_head_packed_bytes(), dtype=torch.uint8, device=w.device)
-        wc = w.detach().contiguous()
-        _hip.check(lib.sdetr_class_head_pack_bf16(_hip.stream_ptr(), wc.data_ptr(), wc.shape[0], 256, packed.data_ptr()),
-                   "class_head_pack")
-        cb = torch.full((96,), float("-inf"), dtype=torch.float32, device=w.device)
-        cb[:wc.shape[0]] = b.detach().float()
-    w.__dict__["_sdetr_cls_frag"] = (tag, packed, cb)
-    return packed, cb
+
+    def build():
+        lib = _hip.lib(w.dtype)
+        with torch.no_grad(), torch.cuda.device(w.device):
+            packed = torch.empty(lib.sdetr_class_head_packed_bytes(), dtype=torch.uint8, device=w.device)
+            wc = w.detach().contiguous()
+            _hip.check(lib.sdetr_class_head_pack_bf16(_hip.stream_ptr(), wc.data_ptr(), wc.shape[0], 256, packed.data_ptr()),
+                       "class_head_pack")
+            cb = torch.full((96,), float("-inf"), dtype=torch.float32, device=w.device)
+            cb[:wc.shape[0]] = b.detach().float()
+        return packed, cb
+    return derived(w, "class_head_fragments", (w, b), build)
 
 
 def prepare_class_score_applies(tokens: Tensor, score, class_head) -> bool:
@@ -1763,11 +1736,7 @@ def token_linear_ln(x: Tensor, linear, norm, residual: Tensor, scatter_index: Op
     if residual.dtype != x.dtype or tuple(residual.shape) != (B, n, 256):
         raise RuntimeError("token_linear_ln: residual must match x")
     packed, b = _packed_linear_bf16(linear.weight, linear.bias)
-    tag = (norm.weight.data_ptr(), norm.weight._version, norm.bias.data_ptr(), norm.bias._version)
-    hit = norm.weight.__dict__.get("_sdetr_f32")
-    if hit is None or hit[0] != tag:
-        hit = (tag, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-        norm.weight.__dict__["_sdetr_f32"] = hit
+    g, be = _norm_f32(norm)
     out_rows = 0
     if scatter_index is not None:
         _hip.require_device("token_linear_ln", scatter_index=scatter_index, scatter_into=scatter_into)
@@ -1780,7 +1749,7 @@ def token_linear_ln(x: Tensor, linear, norm, residual: Tensor, scatter_index: Op
     with torch.cuda.device(x.device):
         code = _hip.lib(x.dtype).sdetr_token_linear_ln_bf16(
             _hip.stream_ptr(), x.data_ptr(), residual.data_ptr(), _batch_stride(residual, "token_linear_ln"), n, B * n,
-            256, packed.data_ptr(), b.data_ptr(), hit[1].data_ptr(), hit[2].data_ptr(), float(norm.eps), out.data_ptr(),
+            256, packed.data_ptr(), b.data_ptr(), g.data_ptr(), be.data_ptr(), float(norm.eps), out.data_ptr(),
             _hip.ptr(scatter_index), out_rows)
     _hip.check(code, "token_linear_ln")
     return out

@@ -14,6 +14,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _hip, pyramid
+from .derived import derived
 from .salience_encoder import SalienceTransformerEncoder, SalienceTransformerEncoderLayer
 from .salience_filtering import MaskPredictor, level_filtering, salience_filtering, token_budgets
 
@@ -60,7 +61,6 @@ class SalienceEncoderHotPath(nn.Module):
         self.encoder_class_head = nn.Linear(self.embed_dim, num_classes)
         self.encoder.enhance_mcsp = self.encoder_class_head
         self.enc_mask_predictor = MaskPredictor(self.embed_dim, self.embed_dim)
-        self._ratio_host = (tuple(float(r) for r in level_filter_ratio), tuple(float(r) for r in layer_filter_ratio))
         # the value projection rides in the stage-1 launches of the two coarsest levels (csrc/fused_head_value.hip):
         # same kernels, two launches' worth of an idle chip put to use
         self.fuse_value_projection = True
@@ -93,13 +93,9 @@ class SalienceEncoderHotPath(nn.Module):
     def _ratios(self):
         """Filter ratios as host floats (float32 values of the registered buffers; refreshed after a
         checkpoint load changed them -- one tiny D2H copy, then cached)."""
-        key = (self.level_filter_ratio._version, self.layer_filter_ratio._version,
-               self.level_filter_ratio.data_ptr())
-        if getattr(self, "_ratio_key", None) != key:
-            self._ratio_host = (tuple(self.level_filter_ratio.detach().cpu().tolist()),
-                                tuple(self.layer_filter_ratio.detach().cpu().tolist()))
-            self._ratio_key = key
-        return self._ratio_host
+        return derived(self, "ratios", (self.level_filter_ratio, self.layer_filter_ratio),
+                       lambda: (tuple(self.level_filter_ratio.detach().cpu().tolist()),
+                                tuple(self.layer_filter_ratio.detach().cpu().tolist())))
 
     # layers of the batched value projection per carrier launch, in carrier order: stage 1 / stage 2 of the coarsest level,
     # of the next one, then stage 2 of the third-coarsest (level_filtering); pieces no launch carried run on their own

@@ -31,6 +31,7 @@ from torch.nn import functional as F
 from torch.nn.init import constant_, xavier_uniform_
 
 from . import _hip
+from .derived import derived, invalidate_caches
 
 
 def _is_power_of_2(n):
@@ -484,17 +485,10 @@ def msda_forward_head_major(value_hm: Tensor, spatial_shapes: Tensor, level_star
 
 def _stacked_value_proj(attn_modules):
     """Concatenated ``value_proj`` weights / biases of the modules, cached on the first one."""
-    first = attn_modules[0]
-    owner = first.__dict__
     ps = [p for m in attn_modules for p in (m.value_proj.weight, m.value_proj.bias)]
-    key = tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-    hit = owner.get("_batched_value_proj")
-    if hit is None or hit[0] != key:
-        w = torch.cat([m.value_proj.weight.detach() for m in attn_modules], 0).contiguous()
-        b = torch.cat([m.value_proj.bias.detach() for m in attn_modules], 0).contiguous()
-        hit = (key, w, b)
-        owner["_batched_value_proj"] = hit
-    return hit[1], hit[2]
+    return derived(attn_modules[0], "stacked_value_proj", ps,
+                   lambda: (torch.cat([w.detach() for w in ps[0::2]], 0).contiguous(),
+                            torch.cat([b.detach() for b in ps[1::2]], 0).contiguous()))
 
 
 def _bordered_levels_for(attn_modules, level_shapes, vdt):
@@ -543,24 +537,6 @@ def batched_value_maps(attn_modules, value: Tensor, padding_mask: Optional[Tenso
     v_all = F.linear(value, w_all, b_all)                      # [B, Nv, n*E]
     out = value_to_head_major(v_all, padding_mask, heads, vdt, num_groups=n)
     return out[None] if n == 1 else out
-
-
-def invalidate_caches(module: nn.Module) -> None:
-    """Drop every derived-weight cache below ``module`` (fused / head-major projection operands, batched value
-    projections, packed MFMA operands of the Linear layers, folded neck plans, flattened background tables).
-
-    The caches are keyed on ``(data_ptr, _version)`` of their parameters, which ``optimizer.step()``, ``load_state_dict``,
-    ``.to()`` and every in-place op on the parameter change.  A write THROUGH ``p.data`` (``p.data.copy_()``, EMA helpers,
-    ``nn.init`` on ``.data``) changes neither: call this function afterwards, or write ``with torch.no_grad(): p.copy_(..)``.
-    """
-    for m in module.modules():
-        for attr in ("_fused_cache", "_fused_hm_cache", "_plan", "_flat_cache", "_enc_output_cast"):
-            if attr in m.__dict__:
-                m.__dict__[attr] = None
-        m.__dict__.pop("_batched_value_proj", None)
-        for p in m.parameters(recurse=False):
-            for key in ("_sdetr_packed", "_sdetr_ffn", "_sdetr_tl", "_sdetr_tl512", "_sdetr_f32"):
-                p.__dict__.pop(key, None)
 
 
 _EXCLUSIVE = threading.local()
@@ -690,7 +666,6 @@ class MultiScaleDeformableAttention(nn.Module):
         self.attention_weights = nn.Linear(embed_dim, num_heads * num_levels * num_points)
         self.value_proj = nn.Linear(embed_dim, embed_dim)
         self.output_proj = nn.Linear(embed_dim, embed_dim)
-        self._fused_cache = None
         self.init_weights()
 
     def init_weights(self):
@@ -716,30 +691,28 @@ class MultiScaleDeformableAttention(nn.Module):
         invalidate_caches(self)
 
     # -- native path pieces --------------------------------------------------------------------
+    def _query_projection_params(self):
+        return (self.sampling_offsets.weight, self.sampling_offsets.bias,
+                self.attention_weights.weight, self.attention_weights.bias)
+
     def _fused_query_projection(self):
         """[sampling_offsets ; attention_weights] as one (384 x 256) GEMM operand, cached per
         parameter version so eval-mode forwards do not re-concatenate."""
-        ps = (self.sampling_offsets.weight, self.sampling_offsets.bias,
-              self.attention_weights.weight, self.attention_weights.bias)
-        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-        if self._fused_cache is None or self._fused_cache[0] != key:
-            w = torch.cat([ps[0].detach(), ps[2].detach()], 0).contiguous()
-            b = torch.cat([ps[1].detach(), ps[3].detach()], 0).contiguous()
-            self._fused_cache = (key, w, b)
-        return self._fused_cache[1], self._fused_cache[2]
+        ps = self._query_projection_params()
+        return derived(self, "fused_query_projection", ps,
+                       lambda: (torch.cat([ps[0].detach(), ps[2].detach()], 0).contiguous(),
+                                torch.cat([ps[1].detach(), ps[3].detach()], 0).contiguous()))
 
     def _fused_query_projection_head_major(self):
         """The same operand with its rows ordered by head -- head m: its 2*L*P offset rows, then its L*P logit rows --
         so that the token-resident projection kernel can store ``[B, M, Nq, 3*L*P]`` directly."""
-        w, b = self._fused_query_projection()
-        hit = getattr(self, "_fused_hm_cache", None)
-        if hit is None or hit[0] is not w:
+        def build():
+            w, b = self._fused_query_projection()
             M, LP = self.num_heads, self.num_levels * self.num_points
             order = torch.cat([torch.cat([torch.arange(m * 2 * LP, (m + 1) * 2 * LP),
                                           M * 2 * LP + torch.arange(m * LP, (m + 1) * LP)]) for m in range(M)]).to(w.device)
-            hit = (w, w[order].contiguous(), b[order].contiguous())
-            self._fused_hm_cache = hit
-        return hit[1], hit[2]
+            return w[order].contiguous(), b[order].contiguous()
+        return derived(self, "fused_query_projection_head_major", self._query_projection_params(), build)
 
     def project_value(self, value: Tensor, key_padding_mask: Optional[Tensor]) -> Tensor:
         """value_proj + padding zero-fill + head-major re-layout -> ``[B, M, Nv, D]``."""

@@ -10,6 +10,8 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
+from .derived import derived
+
 
 def flatten_multi_level(multi_level_elements: Sequence[Tensor]) -> Tensor:
     """``[B,(C),H_l,W_l]`` per level -> token-major ``[B,S,(C)]`` (base_transformer.py:22-27)."""
@@ -164,14 +166,11 @@ class PositionEmbeddingLearned(nn.Module):
     def flat_cached(self, level_shapes: Sequence[Tuple[int, int]], dtype: torch.dtype) -> Tensor:
         """``flat(level_shapes).to(dtype)`` detached, rebuilt only when the embeddings (or the request) change --
         for the no-grad path, where it is a constant of the weights."""
-        ws = (self.row_embed.weight, self.col_embed.weight)
-        key = (tuple(map(tuple, level_shapes)), dtype) + tuple((w.data_ptr(), w._version, str(w.device)) for w in ws)
-        hit = self.__dict__.get("_flat_cache")
-        if hit is None or hit[0] != key:
+        def build():
             with torch.no_grad():
-                hit = (key, self.flat(level_shapes).to(dtype).contiguous())
-            self.__dict__["_flat_cache"] = hit
-        return hit[1]
+                return self.flat(level_shapes).to(dtype).contiguous()
+        return derived(self, "flat", (self.row_embed.weight, self.col_embed.weight), build,
+                       extra=(tuple(map(tuple, level_shapes)), dtype))
 
     def forward(self, mask: Tensor) -> Tensor:
         h, w = mask.shape[-2:]

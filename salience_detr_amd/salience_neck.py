@@ -31,6 +31,7 @@ import torch
 from torch import Tensor, nn
 
 from . import filter_ops as FO
+from .derived import derived
 
 
 class Conv2dNormActivation(nn.Sequential):
@@ -175,7 +176,6 @@ class RepVGGPluXNetwork(nn.Module):
                                                         activation_layer=activation) for _ in range(n - 1))
         self.extra_block = extra_block
         self.process_group = None   # ranks whose pixels share the batch statistics in training mode (None = all)
-        self._plan = None
         self.init_weights()
 
     def init_weights(self):
@@ -188,10 +188,10 @@ class RepVGGPluXNetwork(nn.Module):
 
     # ---- folded parameters ------------------------------------------------------------------------------------------
     def _folded(self, dtype) -> Dict[str, object]:
-        tensors = list(self.parameters()) + list(self.buffers())
-        tag = (dtype, tuple((t.data_ptr(), t._version) for t in tensors))
-        if self._plan is not None and self._plan[0] == tag:
-            return self._plan[1]
+        return derived(self, "folded", list(self.parameters()) + list(self.buffers()), lambda: self._fold(dtype),
+                       extra=dtype)
+
+    def _fold(self, dtype) -> Dict[str, object]:
         plan: Dict[str, object] = dict(lateral=[], layer=[], down=[], pan=[])
         for m in self.lateral_convs:
             w, b = m.folded()
@@ -205,7 +205,6 @@ class RepVGGPluXNetwork(nn.Module):
                                  FO.neck_pack_conv3x3(wd, dtype) if dtype in (torch.bfloat16, torch.float16) and wd.is_cuda else None))
         for m in self.pan_blocks:
             plan["pan"].append(m.folded(dtype))
-        self._plan = (tag, plan)
         return plan
 
     # ---- token-major forward ----------------------------------------------------------------------------------------

@@ -87,6 +87,44 @@ def test_two_rank_gradients_match_single_process(tmp_path, bucket_bytes):
         assert torch.equal(g0[name], g1[name]), name
 
 
+def _attn_model():
+    from salience_detr_amd.ms_deform_attn import MultiScaleDeformableAttention
+    torch.manual_seed(0)
+    m = MultiScaleDeformableAttention(32, 4, 4, 4)
+    m.load_state_dict(syn.det_state_dict(m.state_dict(), num_heads=4))
+    return m
+
+
+def _broadcast_worker(rank, world, port, out_dir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        model = _attn_model()
+        if rank == 1:  # this replica packs its own operand, then its parameters are overwritten through `.data`
+            with torch.no_grad():
+                for p in model.parameters():
+                    p.add_(1.0)
+            model._fused_query_projection()
+        broadcast_parameters(model, src=0)
+        w, b = model._fused_query_projection()
+        torch.save(dict(w=w.clone(), b=b.clone()), os.path.join(out_dir, f"b{rank}.pt"))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_broadcast_parameters_drops_derived_operands(tmp_path):
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.spawn(_broadcast_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    m = _attn_model()
+    want_w = torch.cat([m.sampling_offsets.weight, m.attention_weights.weight]).detach()
+    want_b = torch.cat([m.sampling_offsets.bias, m.attention_weights.bias]).detach()
+    for rank in range(2):
+        got = torch.load(os.path.join(tmp_path, f"b{rank}.pt"))
+        assert torch.equal(got["w"], want_w) and torch.equal(got["b"], want_b), rank
+
+
 # ---- the REAL hot-path parameter list (the module bench.py --mode train reduces): 300+ tensors, the class head shared
 # between `encoder_class_head` and `encoder.enhance_mcsp`, parameters one rank did not use, overlapped bucket hooks ----
 def _hot_path_model():
