@@ -1140,6 +1140,63 @@ int sdetr_attention_train_backward_f32(sdetr_stream_t stream, const float *q, in
                                        int num_rows, int head_dim, float scale, const float *out, const float *lse,
                                        const float *grad_out, float *grad_q, float *grad_k, float *grad_v);
 
+/* ---------------------------------------------------------------------------------------------
+ * Detector input stage (row N7): ChannelMapper (models/necks/channel_mapper.py) convolutions + GroupNorm, per-level
+ * padding masks and sine positions (models/bricks/position_encoding.py:9-67, salience_detr.py:172-176).
+ *
+ * A level: x f32 [batch, in_channels, height, width] NCHW contiguous (16-byte aligned); weight = the conv weight [Co, Cin,
+ * k, k] (f32, contiguous, as [Co, Cin * k * k]) packed by sdetr_frontend_pack_weight with the precision of the conv call
+ * (16-byte aligned); out f32 [batch, out_channels, Ho, Wo]; gamma / beta f32 [out_channels] (GroupNorm affine).  kernel_size 1: bias-free 1x1 stride-1 conv (Ho, Wo = height, width);
+ * kernel_size 3: bias-free 3x3 stride-2 pad-1 conv (Ho = (height - 1) / 2 + 1).  in_channels a multiple of 32; at most 8
+ * levels per call.  Levels of one call are independent (a 3x3 level reading a previous level's NORMALISED output goes in
+ * a later call).
+ *
+ * sdetr_frontend_conv: ONE launch for every level of the call.  precision 0: fp32 accuracy (exact three-way bf16 split
+ * of both operands, six products); 1: one product of the round-to-nearest 16-bit operands (bf16 in libsalience_hip.so,
+ * fp16 in libsalience_hip_f16.so), fp32 accumulation.  kernel_size 1 writes the raw convolution to out and, into the
+ * workspace at the level's offset, GroupNorm partials f32 [batch][out_channels][tiles][2] = (mean, M2) of the channel
+ * over pixel tile t (pixels 128 t .. min(128 t + 128, Ho Wo) - 1); kernel_size 3 writes split-K partial sums f32
+ * [splits][batch][out_channels][Ho Wo] there (their sum over splits is the convolution) and does not touch out.
+ * sdetr_frontend_groupnorm: ONE launch; GroupNorm(num_groups, out_channels, eps) with the affine, in place on out of every
+ * 1x1 level, from the 3x3 partials into out; statistics merged in a fixed order (no atomics, deterministic).
+ * sdetr_frontend_conv_splits: the split count and workspace byte offset of every level (host arrays of n_levels).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_frontend_level {
+    const float *x;
+    const void *weight;
+    int in_channels;
+    int height;
+    int width;
+    int kernel_size;
+    float *out;
+    const float *gamma;
+    const float *beta;
+} sdetr_frontend_level;
+
+/* the packed weight of `count` f32 elements: precision 0 -> three 16-bit planes [3][count] (the exact truncating bf16
+ * split x = p0 + p1 + p2); precision 1 -> one plane [count] rounded to nearest (bf16 in libsalience_hip.so, fp16 in
+ * libsalience_hip_f16.so).  One launch; packed_bytes returns -1 on bad arguments. */
+int64_t sdetr_frontend_packed_bytes(int64_t count, int precision);
+int sdetr_frontend_pack_weight(sdetr_stream_t stream, const float *weight, int64_t count, int precision, void *out);
+int64_t sdetr_frontend_workspace_bytes(const sdetr_frontend_level *levels, int n_levels, int batch, int out_channels);
+int sdetr_frontend_conv_splits(const sdetr_frontend_level *levels, int n_levels, int batch, int out_channels, int *splits,
+                               int64_t *workspace_offsets);
+int sdetr_frontend_conv(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
+                        int out_channels, int precision, void *workspace, int64_t workspace_bytes);
+int sdetr_frontend_groupnorm(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
+                             int out_channels, int num_groups, float eps, const void *workspace, int64_t workspace_bytes);
+
+/* sdetr_frontend_masks_positions: ONE launch for all levels.  mask u8 (bool) [batch, height, width], nonzero on padding.
+ * level_hw: host int array [n_levels][2] = (H_l, W_l).  Per level: level_masks[l] u8 [batch, H_l, W_l] = torch's nearest
+ * down-sample (source pixel min(int(floorf(dst * ((float)in / out))), in - 1)); level_pos[l] f32 [batch, 2F, H_l, W_l]
+ * = PositionEmbeddingSine(F = num_pos_feats) of that mask: per axis the valid-pixel cumsum c and its line total t,
+ * e = normalize ? (c + offset) / (t + eps) * scale : c + offset, feature i = e / dim_t[i] (a true division by the
+ * module's device buffer), sin for even i, cos for odd i; channels (y features, x features).  At most 8 levels. */
+int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, int batch, int height, int width,
+                                   int n_levels, const int *level_hw, const float *dim_ty, const float *dim_tx,
+                                   int num_pos_feats, int normalize, float scale, float eps, float offset,
+                                   uint8_t *const *level_masks, float *const *level_pos);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,13 @@ class SetOutputStruct(ctypes.Structure):
     """``sdetr_set_output`` of include/salience_hip.h."""
     _fields_ = [("logits", ctypes.c_void_p), ("logits_batch_stride", ctypes.c_int64), ("boxes", ctypes.c_void_p),
                 ("boxes_batch_stride", ctypes.c_int64), ("binary_cls", ctypes.c_int)]
+
+
+class FrontendLevelStruct(ctypes.Structure):
+    """``sdetr_frontend_level`` of include/salience_hip.h."""
+    _fields_ = [("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("in_channels", ctypes.c_int),
+                ("height", ctypes.c_int), ("width", ctypes.c_int), ("kernel_size", ctypes.c_int), ("out", ctypes.c_void_p),
+                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p)]
 _i64 = ctypes.c_int64
 _p = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -211,6 +218,13 @@ SIGNATURES = {
     "sdetr_set_loss_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "sdetr_set_loss": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p] + [ctypes.c_float] * 3 + [_p, _i64, _p]),
     "sdetr_set_loss_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p] + [ctypes.c_float] * 3 + [_p, _p, _p]),
+    "sdetr_frontend_packed_bytes": (_i64, [_i64, _i]),
+    "sdetr_frontend_pack_weight": (_i, [_p, _p, _i64, _i, _p]),
+    "sdetr_frontend_workspace_bytes": (_i64, [_p, _i, _i, _i]),
+    "sdetr_frontend_conv_splits": (_i, [_p, _i, _i, _i, _p, _p]),
+    "sdetr_frontend_conv": (_i, [_p, _p, _i, _i, _i, _i, _p, _i64]),
+    "sdetr_frontend_groupnorm": (_i, [_p, _p, _i, _i, _i, _i, ctypes.c_float, _p, _i64]),
+    "sdetr_frontend_masks_positions": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _i] + [ctypes.c_float] * 3 + [_p, _p]),
 }
 
 
