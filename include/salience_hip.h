@@ -1197,6 +1197,72 @@ int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, i
                                    int num_pos_feats, int normalize, float scale, float eps, float offset,
                                    uint8_t *const *level_masks, float *const *level_pos);
 
+/* ---------------------------------------------------------------------------------------------
+ * Backbone (row N0): eval-mode ResNet with FrozenBatchNorm2d (models/backbones/resnet.py, models/bricks/misc.py:9-57) and
+ * the image batching in front of it (models/detectors/base_detector.py:114-126, util/misc.py:75-104).
+ *
+ * precision 0: fp32 accuracy (the activation split exactly into three bf16 terms, the weight packed as three planes, six
+ * products); 1: one product of round-to-nearest 16-bit operands with fp32 accumulation, activations stored in the 16-bit
+ * type between layers (bf16 in libsalience_hip.so, fp16 in libsalience_hip_f16.so).
+ *
+ * sdetr_backbone_pack: folds FrozenBatchNorm2d(gamma, beta, running_mean, running_var, eps) into the bias-free conv weight
+ * f32 [out, in, k, k]: w' = w * gamma / sqrt(var + eps) packed as 16-bit planes [planes][out][K32] (K32 = in * k * k
+ * rounded up to 32, zero columns past it; precision 0: three planes of the exact truncating bf16 split, 1: one plane
+ * rounded to nearest) in reduction order layout 0: k = (ky * k + kx) * in + c (channels-last input), layout 1:
+ * k = c * k * k + ky * k + kx (NCHW input); bias f32 [out] = beta - running_mean * gamma / sqrt(var + eps).
+ *
+ * A conv op (op 0): x = channels-last [batch, height, width, in] in the compute dtype (in % 32 == 0), or with x_nchw the
+ * f32 NCHW canvas [batch, in, height, width] (any in; weight packed with layout 1); out [batch, Ho, Wo, out_channels]
+ * channels-last in the compute dtype, Ho = (height + 2 padding - kernel) / stride + 1; out = relu?(conv' + bias
+ * (+ residual)) with residual shaped as out (or NULL); out_nchw (or NULL): the same values as f32 NCHW [batch, out, Ho,
+ * Wo].  kernel 1..7, stride 1 or 2.  splits: 0 = automatic, n > 0 = n pieces of the reduction (clamped), summed in a
+ * fixed order through the workspace (no atomics: bit-identical from run to run).  x and weight 16-byte aligned.
+ * A max-pool op (op 1): 3x3 stride 2 padding 1 over x channels-last [batch, height, width, in_channels] (in % 8 == 0)
+ * into out [batch, Ho, Wo, in_channels], compute dtype, padding never selected.
+ * sdetr_backbone_run launches a whole plan of ops in order (validated before the first launch); the workspace must hold
+ * sdetr_backbone_workspace_bytes (the largest split-K buffer of the plan).
+ *
+ * sdetr_backbone_batch_images: images = host array of `batch` device pointers to [3, h_i, w_i] (f32 in [0, 1], or u8
+ * when is_uint8: v / 255), image_hw host int [batch][2]; canvas f32 [batch, 3, canvas_height, canvas_width] =
+ * (v - mean[c]) / std[c] (ImageNet mean 0.485 0.456 0.406, std 0.229 0.224 0.225) inside image b, 0 on padding; mask
+ * u8 [batch, canvas_height, canvas_width] = 1 on padding.  At most 64 images.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_backbone_op {
+    int op;
+    const void *x;
+    const void *weight;
+    const float *bias;
+    const void *residual;
+    void *out;
+    float *out_nchw;
+    int batch;
+    int in_channels;
+    int height;
+    int width;
+    int out_channels;
+    int kernel_size;
+    int stride;
+    int padding;
+    int relu;
+    int x_nchw;
+    int splits;
+} sdetr_backbone_op;
+
+int64_t sdetr_backbone_packed_bytes(int out_channels, int in_channels, int kernel_size, int precision);
+int sdetr_backbone_pack(sdetr_stream_t stream, const float *weight, const float *gamma, const float *beta,
+                        const float *running_mean, const float *running_var, float eps, int out_channels, int in_channels,
+                        int kernel_size, int layout, int precision, void *packed, float *bias);
+int sdetr_backbone_conv_splits(const sdetr_backbone_op *op, int precision);
+int64_t sdetr_backbone_workspace_bytes(const sdetr_backbone_op *ops, int n_ops, int precision);
+int sdetr_backbone_conv(sdetr_stream_t stream, const sdetr_backbone_op *op, int precision, void *workspace,
+                        int64_t workspace_bytes);
+int sdetr_backbone_maxpool(sdetr_stream_t stream, const void *x, int batch, int height, int width, int channels,
+                           int precision, void *out);
+int sdetr_backbone_run(sdetr_stream_t stream, const sdetr_backbone_op *ops, int n_ops, int precision, void *workspace,
+                       int64_t workspace_bytes);
+int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
+                                int is_uint8, int canvas_height, int canvas_width, float *canvas, uint8_t *mask);
+
 #ifdef __cplusplus
 }
 #endif

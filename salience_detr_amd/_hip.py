@@ -72,6 +72,15 @@ class FrontendLevelStruct(ctypes.Structure):
     _fields_ = [("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("in_channels", ctypes.c_int),
                 ("height", ctypes.c_int), ("width", ctypes.c_int), ("kernel_size", ctypes.c_int), ("out", ctypes.c_void_p),
                 ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p)]
+
+
+class BackboneOpStruct(ctypes.Structure):
+    """``sdetr_backbone_op`` of include/salience_hip.h."""
+    _fields_ = [("op", ctypes.c_int), ("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("residual", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_nchw", ctypes.c_void_p),
+                ("batch", ctypes.c_int), ("in_channels", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int),
+                ("out_channels", ctypes.c_int), ("kernel_size", ctypes.c_int), ("stride", ctypes.c_int),
+                ("padding", ctypes.c_int), ("relu", ctypes.c_int), ("x_nchw", ctypes.c_int), ("splits", ctypes.c_int)]
 _i64 = ctypes.c_int64
 _p = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -225,6 +234,14 @@ SIGNATURES = {
     "sdetr_frontend_conv": (_i, [_p, _p, _i, _i, _i, _i, _p, _i64]),
     "sdetr_frontend_groupnorm": (_i, [_p, _p, _i, _i, _i, _i, ctypes.c_float, _p, _i64]),
     "sdetr_frontend_masks_positions": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _i] + [ctypes.c_float] * 3 + [_p, _p]),
+    "sdetr_backbone_packed_bytes": (_i64, [_i, _i, _i, _i]),
+    "sdetr_backbone_pack": (_i, [_p] * 6 + [ctypes.c_float] + [_i] * 5 + [_p, _p]),
+    "sdetr_backbone_conv_splits": (_i, [_p, _i]),
+    "sdetr_backbone_workspace_bytes": (_i64, [_p, _i, _i]),
+    "sdetr_backbone_conv": (_i, [_p, _p, _i, _p, _i64]),
+    "sdetr_backbone_maxpool": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "sdetr_backbone_run": (_i, [_p, _p, _i, _i, _p, _i64]),
+    "sdetr_backbone_batch_images": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
 }
 
 

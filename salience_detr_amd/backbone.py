@@ -1,0 +1,448 @@
+"""Row N0 (DESIGN.md §4 "Backbone"): the ResNet backbone in front of ``ChannelMapper`` (reference
+``models/backbones/resnet.py``, ``models/bricks/misc.py:9-57``), eval mode with ``FrozenBatchNorm2d``.
+
+``ResNetBackbone(arch, weights=None, return_indices=(0, 1, 2, 3), freeze_indices=(), **kwargs)`` has the reference's
+constructor, ``num_channels`` and state-dict keys: the reference's feature extractor keeps ``conv1``, ``bn1`` and
+``layer1`` .. ``layer{max(return_indices) + 1}`` under their own names (no ``avgpool`` / ``fc``).  ``forward(x)`` returns ``{"layer{i + 1}": map}`` for
+``i in return_indices``, fp32 NCHW.  ``weights`` is a state dict (optionally under ``"model"``) or a local file path:
+nothing is ever downloaded (``weights=None`` keeps the random initialisation).  Loading is non-strict with shape
+filtering, as the reference's ``util.utils.load_state_dict``; ``num_batches_tracked`` entries are dropped by
+``FrozenBatchNorm2d``.
+
+How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/backbone.hip``:
+  * every conv + its ``FrozenBatchNorm2d`` is ONE implicit-GEMM launch whose epilogue adds the folded bias, the residual
+    and the ReLU; the weight is folded and packed once per parameter version (``derived``);
+  * activations between layers are channels-last in the compute dtype; the last block of each returned stage also
+    writes the stage's fp32 NCHW map; the stem reads the fp32 NCHW canvas; the max pool is a launch of its own;
+  * the whole network is one precomputed plan handed to ``sdetr_backbone_run`` (one ctypes call per forward);
+  * ``set_dtype``: fp32 (default) multiplies at fp32 accuracy (exact three-way bf16 split of both operands); bf16 /
+    fp16 take one 16-bit product with fp32 accumulation and keep the activations in that type between layers.
+The HIP path serves every ``groups == 1`` arch without dilation or DCN: resnet18/34/50/101/152 and wide_resnet50_2 /
+101_2.  Grouped ResNeXt, and every call with grad enabled on something that requires grad, take the plain-torch composite
+(``F.conv2d`` + the frozen affine), which is also the autograd path: training the backbone in HIP is out of scope.  A
+CPU tensor on the HIP form raises: the hot path has no CPU fallback.
+"""
+import ctypes
+import os
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Type, Union
+
+import torch
+from torch import Tensor, nn
+
+from . import _hip
+from .derived import derived
+
+
+class FrozenBatchNorm2d(nn.Module):
+    """BatchNorm2d with fixed statistics and affine (reference ``models/bricks/misc.py:9-57``)."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5):
+        super().__init__()
+        self.eps = eps
+        self.register_buffer("weight", torch.ones(num_features))
+        self.register_buffer("bias", torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        state_dict.pop(prefix + "num_batches_tracked", None)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def forward(self, x: Tensor) -> Tensor:
+        w = self.weight.reshape(1, -1, 1, 1)
+        b = self.bias.reshape(1, -1, 1, 1)
+        rv = self.running_var.reshape(1, -1, 1, 1)
+        rm = self.running_mean.reshape(1, -1, 1, 1)
+        scale = w * (rv + self.eps).rsqrt()
+        bias = b - rm * scale
+        return x * scale + bias
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}({self.weight.shape[0]}, eps={self.eps})"
+
+
+def conv3x3(in_planes: int, out_planes: int, stride: int = 1, groups: int = 1, dilation: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, groups=groups, bias=False,
+                     dilation=dilation)
+
+
+def conv1x1(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(in_planes, out_planes, kernel_size=1, stride=stride, bias=False)
+
+
+class BasicBlock(nn.Module):
+    expansion: int = 1
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: Optional[nn.Module] = None, groups: int = 1,
+                 base_width: int = 64, dilation: int = 1, norm_layer: Optional[Callable[..., nn.Module]] = None,
+                 with_dcn: bool = False):
+        super().__init__()
+        norm_layer = norm_layer or FrozenBatchNorm2d
+        if groups != 1 or base_width != 64:
+            raise ValueError("BasicBlock only supports groups=1 and base_width=64")
+        if dilation > 1:
+            raise NotImplementedError("Dilation > 1 not supported in BasicBlock")
+        if with_dcn:
+            raise NotImplementedError("deformable conv stages are not available (no DeformConv2d in this package)")
+        self.conv1 = conv3x3(inplanes, planes, stride)
+        self.bn1 = norm_layer(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = conv3x3(planes, planes)
+        self.bn2 = norm_layer(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x: Tensor) -> Tensor:
+        identity = x if self.downsample is None else self.downsample(x)
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        out += identity
+        return self.relu(out)
+
+
+class Bottleneck(nn.Module):
+    expansion: int = 4
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: Optional[nn.Module] = None, groups: int = 1,
+                 base_width: int = 64, dilation: int = 1, norm_layer: Optional[Callable[..., nn.Module]] = None,
+                 with_dcn: bool = False):
+        super().__init__()
+        norm_layer = norm_layer or FrozenBatchNorm2d
+        if with_dcn:
+            raise NotImplementedError("deformable conv stages are not available (no DeformConv2d in this package)")
+        width = int(planes * (base_width / 64.0)) * groups
+        self.conv1 = conv1x1(inplanes, width)
+        self.bn1 = norm_layer(width)
+        self.conv2 = conv3x3(width, width, stride, groups, dilation)
+        self.bn2 = norm_layer(width)
+        self.conv3 = conv1x1(width, planes * self.expansion)
+        self.bn3 = norm_layer(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x: Tensor) -> Tensor:
+        identity = x if self.downsample is None else self.downsample(x)
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        out += identity
+        return self.relu(out)
+
+
+class ResNet(nn.Module):
+    """The reference's ``ResNet`` without ``avgpool`` / ``fc`` (which its feature extractor drops); ``num_stages`` keeps
+    only ``layer1`` .. ``layer{num_stages}``, as the extractor does for its deepest returned stage.  ``norm_layer``
+    defaults to ``FrozenBatchNorm2d``."""
+
+    def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: Sequence[int], num_classes: int = 1000,
+                 zero_init_residual: bool = False, groups: int = 1, width_per_group: int = 64,
+                 replace_stride_with_dilation: Optional[List[bool]] = None, stage_with_dcn: Optional[List[bool]] = None,
+                 norm_layer: Optional[Callable[..., nn.Module]] = None, num_stages: int = 4):
+        super().__init__()
+        stage_with_dcn = stage_with_dcn or [False] * 4
+        self._norm_layer = norm_layer = norm_layer or FrozenBatchNorm2d
+        self.inplanes, self.dilation = 64, 1
+        replace_stride_with_dilation = replace_stride_with_dilation or [False, False, False]
+        if len(replace_stride_with_dilation) != 3:
+            raise ValueError("replace_stride_with_dilation should be None or a 3-element tuple, "
+                             f"got {replace_stride_with_dilation}")
+        self.groups, self.base_width, self.block = groups, width_per_group, block
+        self.conv1 = nn.Conv2d(3, self.inplanes, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = norm_layer(self.inplanes)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        for i in range(num_stages):
+            setattr(self, f"layer{i + 1}", self._make_layer(block, 64 * 2 ** i, layers[i], stride=1 if i == 0 else 2,
+                                                            dilate=i > 0 and replace_stride_with_dilation[i - 1],
+                                                            with_dcn=stage_with_dcn[i]))
+        self.num_stages = num_stages
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        if zero_init_residual:
+            for m in self.modules():
+                if isinstance(m, Bottleneck):
+                    nn.init.constant_(m.bn3.weight, 0)
+                elif isinstance(m, BasicBlock):
+                    nn.init.constant_(m.bn2.weight, 0)
+
+    def _make_layer(self, block, planes: int, blocks: int, stride: int = 1, dilate: bool = False,
+                    with_dcn: bool = False) -> nn.Sequential:
+        norm_layer, downsample, previous_dilation = self._norm_layer, None, self.dilation
+        if dilate:
+            self.dilation *= stride
+            stride = 1
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(conv1x1(self.inplanes, planes * block.expansion, stride),
+                                       norm_layer(planes * block.expansion))
+        layers = [block(self.inplanes, planes, stride, downsample, self.groups, self.base_width, previous_dilation,
+                        norm_layer, with_dcn)]
+        self.inplanes = planes * block.expansion
+        for _ in range(1, blocks):
+            layers.append(block(self.inplanes, planes, groups=self.groups, base_width=self.base_width,
+                                dilation=self.dilation, norm_layer=norm_layer, with_dcn=with_dcn))
+        return nn.Sequential(*layers)
+
+    def stages(self) -> List[nn.Sequential]:
+        return [getattr(self, f"layer{i + 1}") for i in range(self.num_stages)]
+
+
+ARCHS = {
+    "resnet18": dict(block=BasicBlock, layers=(2, 2, 2, 2)),
+    "resnet34": dict(block=BasicBlock, layers=(3, 4, 6, 3)),
+    "resnet50": dict(block=Bottleneck, layers=(3, 4, 6, 3)),
+    "resnet101": dict(block=Bottleneck, layers=(3, 4, 23, 3)),
+    "resnet152": dict(block=Bottleneck, layers=(3, 8, 36, 3)),
+    "resnext50_32x4d": dict(block=Bottleneck, layers=(3, 4, 6, 3), groups=32, width_per_group=4),
+    "resnext101_32x4d": dict(block=Bottleneck, layers=(3, 4, 23, 3), groups=32, width_per_group=4),
+    "resnext101_32x8d": dict(block=Bottleneck, layers=(3, 4, 23, 3), groups=32, width_per_group=8),
+    "resnext101_64x4d": dict(block=Bottleneck, layers=(3, 4, 23, 3), groups=64, width_per_group=4),
+    "wide_resnet50_2": dict(block=Bottleneck, layers=(3, 4, 6, 3), width_per_group=128),
+    "wide_resnet101_2": dict(block=Bottleneck, layers=(3, 4, 23, 3), width_per_group=128),
+}
+
+
+def _out_hw(n: int, k: int, s: int, p: int) -> int:
+    return (n + 2 * p - k) // s + 1
+
+
+def plan_shapes(block, layers: Sequence[int], num_stages: int, height: int, width: int, width_per_group: int = 64
+                ) -> List[Tuple[str, int, int, int]]:
+    """``(name, channels, H, W)`` of the stem, the max pool and every stage's output for an ``H x W`` canvas."""
+    h, w = _out_hw(height, 7, 2, 3), _out_hw(width, 7, 2, 3)
+    shapes = [("stem", 64, h, w)]
+    h, w = _out_hw(h, 3, 2, 1), _out_hw(w, 3, 2, 1)
+    shapes.append(("maxpool", 64, h, w))
+    for i in range(num_stages):
+        if i > 0:
+            h, w = _out_hw(h, 3, 2, 1), _out_hw(w, 3, 2, 1)   # the 3x3 / 1x1 stride-2 convs agree on this
+        shapes.append((f"layer{i + 1}", 64 * 2 ** i * block.expansion, h, w))
+    return shapes
+
+
+class ResNetBackbone(nn.Module):
+    def __init__(self, arch: str, weights: Union[None, str, Dict[str, Tensor]] = None,
+                 return_indices: Tuple[int, ...] = (0, 1, 2, 3), freeze_indices: Tuple[int, ...] = (), **kwargs):
+        super().__init__()
+        if arch not in ARCHS:
+            raise ValueError(f"Expected architecture in {tuple(ARCHS)} but got {arch}")
+        config = dict(ARCHS[arch])
+        config.update({k: v for k, v in kwargs.items() if v is not None})
+        config.pop("url", None)
+        self.return_indices = tuple(return_indices)
+        net = ResNet(num_stages=max(self.return_indices) + 1, **config)
+        self.conv1, self.bn1, self.relu, self.maxpool = net.conv1, net.bn1, net.relu, net.maxpool
+        self.num_stages = net.num_stages
+        for i in range(net.num_stages):
+            setattr(self, f"layer{i + 1}", getattr(net, f"layer{i + 1}"))
+        self.block, self.groups, self.width_per_group = net.block, net.groups, net.base_width
+        self.dilation = net.dilation
+        self.num_channels = [64 * self.block.expansion * 2 ** i for i in self.return_indices]
+        self.compute_dtype = torch.float32
+        if weights is not None:
+            self.load_weights(weights)
+        if len(freeze_indices) > 0:
+            for m in (self.conv1, self.bn1):
+                self._freeze(m)
+        for i in freeze_indices:
+            self._freeze(getattr(self, f"layer{i + 1}"))
+
+    @staticmethod
+    def _freeze(module: nn.Module):
+        module.eval()
+        for p in module.parameters():
+            p.requires_grad = False
+
+    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
+        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
+        match are skipped (``util.utils.load_state_dict`` of the reference).  Never downloads."""
+        if isinstance(weights, str):
+            if not os.path.exists(weights):
+                raise FileNotFoundError(f"ResNetBackbone: no weight file at {weights} (nothing is downloaded)")
+            weights = torch.load(weights, map_location="cpu")
+        if "model" in weights and isinstance(weights["model"], dict):
+            weights = weights["model"]
+        own = self.state_dict()
+        matched = {k: v for k, v in weights.items()
+                   if k not in own or k.endswith("num_batches_tracked") or own[k].shape == v.shape}
+        return self.load_state_dict(matched, strict=False)
+
+    def stages(self) -> List[nn.Sequential]:
+        return [getattr(self, f"layer{i + 1}") for i in range(self.num_stages)]
+
+    def set_dtype(self, dtype: torch.dtype):
+        """Precision of the convolutions: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16``
+        (one 16-bit product, fp32 accumulation, 16-bit activations between layers).  The outputs stay fp32."""
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"ResNetBackbone.set_dtype: {dtype} is not float32 / bfloat16 / float16")
+        self.compute_dtype = dtype
+        return self
+
+    # ------------------------------------------------------------------------------------------ form checks
+    def _convs(self):
+        yield self.conv1
+        for stage in self.stages():
+            for blk in stage:
+                for m in blk.modules():
+                    if isinstance(m, nn.Conv2d):
+                        yield m
+
+    def hip_form(self) -> bool:
+        """True when every conv is one the HIP kernels serve (see the module docstring)."""
+        if self.groups != 1 or self.dilation != 1:
+            return False
+        for c in self._convs():
+            if c.groups != 1 or c.dilation != (1, 1) or c.bias is not None:
+                return False
+            if c is not self.conv1 and (c.in_channels % 32 or c.out_channels % 8):
+                return False
+        norms = [self.bn1] + [m for stage in self.stages() for blk in stage for name, m in blk.named_modules()
+                              if name in ("bn1", "bn2", "bn3", "downsample.1")]
+        return all(isinstance(m, FrozenBatchNorm2d) for m in norms)
+
+    def _needs_autograd(self, x: Tensor) -> bool:
+        if not torch.is_grad_enabled():
+            return False
+        return x.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    # ------------------------------------------------------------------------------------------ forward
+    def forward(self, x: Tensor) -> Dict[str, Tensor]:
+        if self._needs_autograd(x) or not self.hip_form():
+            return self.forward_torch(x)
+        return self.forward_hip(x)
+
+    def forward_torch(self, x: Tensor) -> Dict[str, Tensor]:
+        """The differentiable composite (``F.conv2d`` + the frozen affine) on the input's device."""
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        outs = {}
+        for i, stage in enumerate(self.stages()):
+            x = stage(x)
+            if i in self.return_indices:
+                outs[f"layer{i + 1}"] = x
+        return outs
+
+    def _precision(self) -> int:
+        return 0 if self.compute_dtype == torch.float32 else 1
+
+    def _lib(self):
+        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
+
+    def _packed(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d, layout: int) -> Tuple[Tensor, Tensor]:
+        """``(packed weight, folded bias)`` of ``conv`` + ``bn`` (``sdetr_backbone_pack``), built once per parameter
+        version, precision and compute dtype."""
+        precision, lib = self._precision(), self._lib()
+        co, ci, k = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+
+        def build():
+            f32 = [t.detach().to(torch.float32).contiguous() for t in
+                   (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+            nbytes = lib.sdetr_backbone_packed_bytes(co, ci, k, precision)
+            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=f32[0].device)
+            bias = torch.empty(co, dtype=torch.float32, device=f32[0].device)
+            _hip.check(lib.sdetr_backbone_pack(_hip.stream_ptr(), *[t.data_ptr() for t in f32], float(bn.eps), co, ci, k,
+                                               layout, precision, packed.data_ptr(), bias.data_ptr()),
+                       "ResNetBackbone (pack)", lib)
+            return packed, bias
+        return derived(conv, "backbone_packed", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build,
+                       extra=(float(bn.eps), precision, self.compute_dtype, layout))
+
+    def build_plan(self, x: Tensor, splits: int = 0):
+        """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep)`` where
+        ``outputs`` are the returned fp32 NCHW maps and ``keep`` every tensor the plan points into."""
+        act = torch.float32 if self._precision() == 0 else self.compute_dtype
+        dev, batch = x.device, x.shape[0]
+        ops: List[_hip.BackboneOpStruct] = []
+        keep: List[Tensor] = [x]
+        outputs: Dict[str, Tensor] = {}
+
+        def conv_op(conv, bn, src, h, w, relu, residual=None, nchw_out=None, x_nchw=False):
+            k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+            ho, wo = _out_hw(h, k, s, p), _out_hw(w, k, s, p)
+            packed, bias = self._packed(conv, bn, 1 if x_nchw else 0)
+            out = torch.empty(batch, ho, wo, conv.out_channels, device=dev, dtype=act)
+            keep.extend((packed, bias, out))
+            ops.append(_hip.BackboneOpStruct(0, src.data_ptr(), packed.data_ptr(), bias.data_ptr(), _hip.ptr(residual),
+                                             out.data_ptr(), _hip.ptr(nchw_out), batch, conv.in_channels, h, w,
+                                             conv.out_channels, k, s, p, 1 if relu else 0, 1 if x_nchw else 0, splits))
+            return out, ho, wo
+
+        h, w = x.shape[2], x.shape[3]
+        y, h, w = conv_op(self.conv1, self.bn1, x, h, w, True, x_nchw=True)
+        ho, wo = _out_hw(h, 3, 2, 1), _out_hw(w, 3, 2, 1)
+        pooled = torch.empty(batch, ho, wo, 64, device=dev, dtype=act)
+        keep.append(pooled)
+        ops.append(_hip.BackboneOpStruct(1, y.data_ptr(), None, None, None, pooled.data_ptr(), None, batch, 64, h, w, 64,
+                                         3, 2, 1, 0, 0, 0))
+        y, h, w = pooled, ho, wo
+        for i, stage in enumerate(self.stages()):
+            for j, blk in enumerate(stage):
+                last = i in self.return_indices and j == len(stage) - 1
+                nchw = None
+                if last:
+                    nchw = torch.empty(batch, self._block_out_channels(blk), _out_hw(h, 1, blk.stride, 0),
+                                       _out_hw(w, 1, blk.stride, 0), device=dev, dtype=torch.float32)
+                    keep.append(nchw)
+                    outputs[f"layer{i + 1}"] = nchw
+                identity = y
+                if blk.downsample is not None:
+                    identity, _, _ = conv_op(blk.downsample[0], blk.downsample[1], y, h, w, False)
+                t, th, tw = conv_op(blk.conv1, blk.bn1, y, h, w, True)
+                if isinstance(blk, Bottleneck):
+                    t, th, tw = conv_op(blk.conv2, blk.bn2, t, th, tw, True)
+                    y, h, w = conv_op(blk.conv3, blk.bn3, t, th, tw, True, residual=identity, nchw_out=nchw)
+                else:
+                    y, h, w = conv_op(blk.conv2, blk.bn2, t, th, tw, True, residual=identity, nchw_out=nchw)
+        return ops, outputs, keep
+
+    @staticmethod
+    def _block_out_channels(blk) -> int:
+        return blk.conv3.out_channels if isinstance(blk, Bottleneck) else blk.conv2.out_channels
+
+    def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+        if x.dtype != torch.float32:
+            x = x.float()
+        _hip.require_device("ResNetBackbone", x=x)
+        for t in list(self.parameters()) + list(self.buffers()):
+            _hip.require_device("ResNetBackbone", parameter=t.detach())
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"ResNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
+        ops, outputs, keep = self.build_plan(x, splits)
+        lib, precision = self._lib(), self._precision()
+        arr = (_hip.BackboneOpStruct * len(ops))(*ops)
+        ws_bytes = lib.sdetr_backbone_workspace_bytes(arr, len(ops), precision)
+        if ws_bytes < 0:
+            _hip.check(-1, "ResNetBackbone (workspace)", lib)
+        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
+        _hip.check(lib.sdetr_backbone_run(_hip.stream_ptr(), arr, len(ops), precision, ws.data_ptr(), ws_bytes),
+                   "ResNetBackbone (run)", lib)
+        return outputs
+
+
+def batch_images(images: Sequence[Tensor], size_divisible: int = 32) -> Tuple[Tensor, Tensor]:
+    """ONE launch: ``images`` ``[3, h_i, w_i]`` (float in [0, 1], or uint8 read as ``v / 255``) normalised with the
+    ImageNet mean / std and padded with 0 after normalisation into ``canvas`` ``[B, 3, Hp, Wp]`` (Hp, Wp = the largest
+    size rounded up to ``size_divisible``) and ``mask`` ``[B, Hp, Wp]`` (bool, True on padding): the reference's eval
+    ``ConvertImageDtype`` + ``Normalize`` + ``image_list_from_tensors`` + ``construct_mask``."""
+    if len(images) == 0:
+        raise ValueError("batch_images: no images")
+    dev, dt = images[0].device, images[0].dtype
+    if dt not in (torch.float32, torch.uint8):
+        raise RuntimeError(f"batch_images: images must be float32 or uint8, got {dt}")
+    for im in images:
+        if im.dim() != 3 or im.shape[0] != 3 or im.dtype != dt or im.device != dev:
+            raise RuntimeError("batch_images: every image must be [3, h, w] of one dtype on one device")
+        _hip.require_device("batch_images", image=im)
+    hp = -(-max(int(im.shape[1]) for im in images) // size_divisible) * size_divisible
+    wp = -(-max(int(im.shape[2]) for im in images) // size_divisible) * size_divisible
+    canvas = torch.empty(len(images), 3, hp, wp, device=dev, dtype=torch.float32)
+    mask = torch.empty(len(images), hp, wp, device=dev, dtype=torch.bool)
+    ptrs = (ctypes.c_void_p * len(images))(*[im.data_ptr() for im in images])
+    hw = (ctypes.c_int * (2 * len(images)))(*[int(v) for im in images for v in im.shape[1:]])
+    lib = _hip.lib()
+    _hip.check(lib.sdetr_backbone_batch_images(_hip.stream_ptr(), ptrs, hw, len(images), 1 if dt == torch.uint8 else 0, hp,
+                                               wp, canvas.data_ptr(), mask.data_ptr()), "batch_images", lib)
+    return canvas, mask

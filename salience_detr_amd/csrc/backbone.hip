@@ -1,0 +1,685 @@
+// The detector's backbone (row N0): eval-mode ResNet with FrozenBatchNorm2d (reference models/backbones/resnet.py,
+// models/bricks/misc.py:9-57) and the image batching in front of it (base_detector.py:114-126, util/misc.py:75-104).
+//
+//   backbone_pack_kernel      folds FrozenBatchNorm2d into the conv (w' = w * g / sqrt(var + eps), b' = beta - mean * g /
+//                             sqrt(var + eps)) and writes w' in the GEMM's reduction order: three bf16 planes of the exact
+//                             truncating split (fp32 mode) or one 16-bit plane rounded to nearest (16-bit mode)
+//   backbone_conv_kernel      implicit-GEMM convolution C[pixel, co] = sum_k X[pixel, k] W'[co, k] on the matrix cores,
+//                             epilogue relu?(acc + b'[co] (+ residual)), channels-last output in the compute dtype and,
+//                             for the last block of a returned stage, an fp32 NCHW copy; split over K when the tile grid
+//                             is small, the pieces summed in a fixed order by backbone_splitk_kernel (no atomics)
+//   backbone_maxpool_kernel   3x3 stride-2 pad-1 max pool, channels-last
+//   backbone_batch_kernel     normalise (ImageNet mean / std) and pad a list of images into one canvas + padding mask
+//
+// Tiles: 256 pixels x 128 output channels x 32 reduction indices, 8 waves of 64 x 64 (2 x 2 v_mfma_f32_32x32x16 per
+// 16-deep half step), the shape of gemm_x3.hip's second-generation kernel: the activation operand A (pixels) in LDS as
+// fp32 rows split into three bf16 terms fragment by fragment (fp32 mode) or as 16-bit rows; the weight operand B as its
+// pre-split planes.  Two LDS stages: the next tile is loaded into registers while the current one is multiplied, one
+// barrier per step.  Activations between layers are channels-last [B, H, W, C] in the compute dtype (fp32 or the
+// library's 16-bit type), so with C a multiple of 32 one reduction tile is one filter tap of 32 contiguous channels
+// (reduction order k = (ky * kw + kx) * C + c).  The stem reads the fp32 NCHW canvas directly with a per-element gather
+// (reduction order k = c * kh * kw + ky * kw + kx, K = 147 padded to 160 with zero weight columns).
+#include <algorithm>
+#include <type_traits>
+
+#include "common.h"
+
+namespace sdetr {
+namespace {
+
+constexpr int kBM = 256, kBN = 128, kBK = 32, kBThreads = 512;
+constexpr int kBRow32 = kBK * 4 + 16;   // bytes per fp32 activation row in LDS (144)
+constexpr int kBRow16 = kBK * 2 + 16;   // bytes per 16-bit row in LDS (80)
+constexpr int kBPlane = kBN * kBRow16;  // 10 240: one weight plane
+constexpr int kBMaxImages = 64;
+
+template <bool X3>
+struct BCfg {
+    static constexpr int kA = kBM * (X3 ? kBRow32 : kBRow16);   // 36 864 | 20 480
+    static constexpr int kB = (X3 ? 3 : 1) * kBPlane;           // 30 720 | 10 240
+    static constexpr int kStage = kA + kB;
+    static constexpr int kLds = 2 * kStage;                     // 135 168 | 61 440
+};
+
+typedef __bf16 b_bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float b_f32x16_t __attribute__((ext_vector_type(16)));
+
+struct BConv {
+    const char *x;          // NHWC compute dtype, or (nchw) the fp32 NCHW canvas
+    const uint16_t *w;      // packed [planes][co][kpad]
+    const float *bias;      // folded [co]
+    const char *res;        // NHWC [M][co] compute dtype, or null
+    char *out;              // NHWC [M][co] compute dtype
+    float *out_nchw;        // fp32 NCHW [B][co][Ho][Wo], or null
+    float *partial;         // split-K pieces [splits][M][co]
+    uint32_t x_bytes, w_bytes;
+    int batch, ci, h, w_in, co, ks, stride, pad, ho, wo, M, K, kpad, relu, splits, k_per_split;
+    int64_t plane;          // co * kpad
+};
+
+__device__ __forceinline__ int b_acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+__device__ __forceinline__ uint32_t b_off(bool ok, uint32_t off) { return ok ? off : 0xfffffff0u; }
+__device__ __forceinline__ uint32_t b_pack_hi(float lo, float hi)
+{
+    return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
+}
+struct BFrag3 {
+    u32x4_t p[3];
+};
+// exact three-way bf16 split of 8 fp32 values (truncation), as gemm_x3.hip / frontend.hip
+__device__ __forceinline__ BFrag3 b_split(const float4 lo, const float4 hi)
+{
+    const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    float r1[8], r2[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        r1[i] = x[i] - __uint_as_float(__float_as_uint(x[i]) & 0xffff0000u);
+        r2[i] = r1[i] - __uint_as_float(__float_as_uint(r1[i]) & 0xffff0000u);
+    }
+    BFrag3 f;
+    f.p[0] = u32x4_t{b_pack_hi(x[0], x[1]), b_pack_hi(x[2], x[3]), b_pack_hi(x[4], x[5]), b_pack_hi(x[6], x[7])};
+    f.p[1] = u32x4_t{b_pack_hi(r1[0], r1[1]), b_pack_hi(r1[2], r1[3]), b_pack_hi(r1[4], r1[5]), b_pack_hi(r1[6], r1[7])};
+    f.p[2] = u32x4_t{b_pack_hi(r2[0], r2[1]), b_pack_hi(r2[2], r2[3]), b_pack_hi(r2[4], r2[5]), b_pack_hi(r2[6], r2[7])};
+    return f;
+}
+__device__ __forceinline__ b_f32x16_t b_mfma_bf16(u32x4_t a, u32x4_t b, b_f32x16_t c)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b_bf16x8_t, a), __builtin_bit_cast(b_bf16x8_t, b), c, 0,
+                                                   0, 0);
+}
+
+// where output pixel m reads its taps: input row / column of tap (0, 0) and the image's first element
+struct RowInfo {
+    int iy0, ix0, base;
+};
+__device__ __forceinline__ RowInfo row_info(const BConv &c, int m, int base_scale)
+{
+    RowInfo r;
+    if (m >= c.M) {
+        r.iy0 = -(1 << 28);   // every tap out of range: the row reads zeros
+        r.ix0 = 0;
+        r.base = 0;
+        return r;
+    }
+    const int hw = c.ho * c.wo, n = m / hw, rem = m - n * hw, oy = rem / c.wo, ox = rem - oy * c.wo;
+    r.iy0 = oy * c.stride - c.pad;
+    r.ix0 = ox * c.stride - c.pad;
+    r.base = n * base_scale;
+    return r;
+}
+
+// A tile, channels-last input (C % 32 == 0): one tap, 32 contiguous channels per pixel row; 16-byte pieces.
+// fp32: 8 pieces per row, rows tid / 8 + 64 j (j < 4); 16-bit: 4 pieces per row, rows tid / 4 + 128 j (j < 2).
+template <bool X3>
+struct ALoadNHWC {
+    static constexpr int kRows = X3 ? 4 : 2, kStep = X3 ? 64 : 128, kShift = X3 ? 3 : 2, kEsz = X3 ? 4 : 2;
+    RowInfo ri[kRows];
+    uint4 v[kRows];
+    __device__ __forceinline__ void init(const BConv &c, int m0, int tid)
+    {
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) ri[j] = row_info(c, m0 + (tid >> kShift) + kStep * j, c.h * c.w_in);
+    }
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t rs, int k0, int kend, int tid)
+    {
+        const int tap = k0 / c.ci, c0 = k0 - tap * c.ci, ky = tap / c.ks, kx = tap - ky * c.ks;
+        const uint32_t piece = 16u * (uint32_t)(tid & ((1 << kShift) - 1));
+        const bool kok = k0 < kend;
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            const int iy = ri[j].iy0 + ky, ix = ri[j].ix0 + kx;
+            const bool ok = kok && (unsigned)iy < (unsigned)c.h && (unsigned)ix < (unsigned)c.w_in;
+            const uint32_t pix = (uint32_t)ri[j].base + (uint32_t)iy * (uint32_t)c.w_in + (uint32_t)ix;   // (wraps when !ok)
+            v[j] = buffer_load16(rs, b_off(ok, (pix * (uint32_t)c.ci + (uint32_t)c0) * kEsz + piece));
+        }
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        constexpr int row = X3 ? kBRow32 : kBRow16;
+        char *d = tile + (tid >> kShift) * row + 16 * (tid & ((1 << kShift) - 1));
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) *reinterpret_cast<uint4 *>(d + kStep * j * row) = v[j];
+    }
+};
+
+// A tile, the stem: fp32 NCHW canvas, any channel count; 16 reduction indices of one pixel row per thread
+template <bool X3>
+struct ALoadNCHW {
+    RowInfo ri;
+    float v[16];
+    __device__ __forceinline__ void init(const BConv &c, int m0, int tid)
+    {
+        ri = row_info(c, m0 + (tid >> 1), c.ci * c.h * c.w_in);
+    }
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t, int k0, int kend, int tid)
+    {
+        const float *x = reinterpret_cast<const float *>(c.x);
+        const int kk2 = c.ks * c.ks, kb = k0 + 16 * (tid & 1), kmax = min(kend, c.K);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int k = kb + e, ci = k / kk2, t = k - ci * kk2, ky = t / c.ks, kx = t - ky * c.ks;
+            const int iy = ri.iy0 + ky, ix = ri.ix0 + kx;
+            const bool ok = k < kmax && (unsigned)iy < (unsigned)c.h && (unsigned)ix < (unsigned)c.w_in;
+            v[e] = ok ? x[ri.base + ((int64_t)ci * c.h + iy) * c.w_in + ix] : 0.f;
+        }
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        if (X3) {
+            char *d = tile + (tid >> 1) * kBRow32 + 64 * (tid & 1);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                *reinterpret_cast<float4 *>(d + 16 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        } else {
+            char *d = tile + (tid >> 1) * kBRow16 + 32 * (tid & 1);
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                *reinterpret_cast<uint4 *>(d + 16 * q) =
+                    make_uint4(pack_act2(v[8 * q], v[8 * q + 1]), pack_act2(v[8 * q + 2], v[8 * q + 3]),
+                               pack_act2(v[8 * q + 4], v[8 * q + 5]), pack_act2(v[8 * q + 6], v[8 * q + 7]));
+        }
+    }
+};
+
+// B tile: the packed weight, 128 output channels x 32 reduction indices per plane, 16 bytes per thread and plane
+template <int PL>
+struct BLoadW {
+    uint4 q[PL];
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t rs, int n0, int k0, int kend, int tid)
+    {
+        const int r = n0 + (tid >> 2), k = k0 + 8 * (tid & 3);
+        const bool ok = r < c.co && k < kend;
+        const uint32_t o = ((uint32_t)r * (uint32_t)c.kpad + (uint32_t)k) * 2u, plane = (uint32_t)(c.plane * 2);
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) q[pl] = buffer_load16(rs, b_off(ok, o + pl * plane));
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        char *d = tile + (tid >> 2) * kBRow16 + 16 * (tid & 3);
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) *reinterpret_cast<uint4 *>(d + pl * kBPlane) = q[pl];
+    }
+};
+
+// one half step (16 reduction indices) of a wave's 64 x 64 tile
+template <bool X3>
+__device__ __forceinline__ void half_step(const char *fa, const char *fb, int kk, b_f32x16_t (&acc)[2][2])
+{
+    if (X3) {
+        BFrag3 a[2], b[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const float4 *qa = reinterpret_cast<const float4 *>(fa + t * 32 * kBRow32 + kk * 64);
+            a[t] = b_split(qa[0], qa[1]);
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                b[t].p[pl] = *reinterpret_cast<const u32x4_t *>(fb + t * 32 * kBRow16 + pl * kBPlane + kk * 32);
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                b_f32x16_t c = acc[rt][ct];
+                c = b_mfma_bf16(a[rt].p[2], b[ct].p[0], c);   // smallest terms first
+                c = b_mfma_bf16(a[rt].p[0], b[ct].p[2], c);
+                c = b_mfma_bf16(a[rt].p[1], b[ct].p[1], c);
+                c = b_mfma_bf16(a[rt].p[1], b[ct].p[0], c);
+                c = b_mfma_bf16(a[rt].p[0], b[ct].p[1], c);
+                c = b_mfma_bf16(a[rt].p[0], b[ct].p[0], c);
+                acc[rt][ct] = c;
+            }
+    } else {
+        uint4 a[2], b[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            a[t] = *reinterpret_cast<const uint4 *>(fa + t * 32 * kBRow16 + kk * 32);
+            b[t] = *reinterpret_cast<const uint4 *>(fb + t * 32 * kBRow16 + kk * 32);
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[rt][ct] = mfma_act_32x32x16(a[rt], b[ct], acc[rt][ct]);
+    }
+}
+
+// relu?(v + b'[co] (+ residual)) -> out (NHWC, compute dtype) and the fp32 NCHW copy
+template <bool X3>
+__device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
+{
+    v += c.bias[co];
+    const int64_t e = (int64_t)m * c.co + co;
+    if (c.res) {
+        if (X3) v += reinterpret_cast<const float *>(c.res)[e];
+        else v += act_lo(reinterpret_cast<const uint16_t *>(c.res)[e]);
+    }
+    if (c.relu) v = fmaxf(v, 0.f);
+    if (X3) reinterpret_cast<float *>(c.out)[e] = v;
+    else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
+    if (c.out_nchw) {
+        const int hw = c.ho * c.wo, n = m / hw, pix = m - n * hw;
+        c.out_nchw[((int64_t)n * c.co + co) * hw + pix] = v;
+    }
+}
+
+template <bool X3, bool NCHW>
+__global__ void __launch_bounds__(kBThreads, 1) backbone_conv_kernel(BConv c)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    using Cfg = BCfg<X3>;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.x * kBM, n0 = blockIdx.y * kBN;
+    const int kbeg = blockIdx.z * c.k_per_split, kend = min(c.kpad, kbeg + c.k_per_split);
+    const __amdgpu_buffer_rsrc_t rx = make_uniform_rsrc(c.x, c.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_uniform_rsrc(reinterpret_cast<const char *>(c.w), c.w_bytes);
+
+    b_f32x16_t acc[2][2];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[rt][ct][i] = 0.f;
+
+    typename std::conditional<NCHW, ALoadNCHW<X3>, ALoadNHWC<X3>>::type ta;
+    BLoadW<X3 ? 3 : 1> tb;
+    ta.init(c, m0, tid);
+    ta.load(c, rx, kbeg, kend, tid);
+    tb.load(c, rw, n0, kbeg, kend, tid);
+    ta.store(lds, tid);
+    tb.store(lds + Cfg::kA, tid);
+    __syncthreads();
+    const int fa = X3 ? (64 * wm + (lane & 31)) * kBRow32 + (lane >> 5) * 32 : (64 * wm + (lane & 31)) * kBRow16 + (lane >> 5) * 16;
+    const int fb = Cfg::kA + (64 * wn + (lane & 31)) * kBRow16 + (lane >> 5) * 16;
+    int cur = 0;
+    for (int k0 = kbeg; k0 < kend; k0 += kBK) {
+        const bool more = k0 + kBK < kend;   // (uniform)
+        if (more) {                          // the next tile travels in registers while this one is multiplied
+            ta.load(c, rx, k0 + kBK, kend, tid);
+            tb.load(c, rw, n0, k0 + kBK, kend, tid);
+        }
+        const char *s = lds + cur * Cfg::kStage;
+        half_step<X3>(s + fa, s + fb, 0, acc);
+        half_step<X3>(s + fa, s + fb, 1, acc);
+        if (more) {   // the other stage's last readers passed the previous barrier
+            char *d = lds + (cur ^ 1) * Cfg::kStage;
+            ta.store(d, tid);
+            tb.store(d + Cfg::kA, tid);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const int co = n0 + 64 * wn + 32 * ct + (lane & 31);
+        if (co >= c.co) continue;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int m = m0 + 64 * wm + 32 * rt + b_acc_row(i, lane);
+                if (m >= c.M) continue;
+                if (c.splits > 1) c.partial[((int64_t)blockIdx.z * c.M + m) * c.co + co] = acc[rt][ct][i];
+                else emit<X3>(c, m, co, acc[rt][ct][i]);
+            }
+    }
+}
+
+// the split-K pieces summed in split order (deterministic), then the epilogue
+template <bool X3>
+__global__ void __launch_bounds__(256) backbone_splitk_kernel(BConv c)
+{
+    const int64_t total = (int64_t)c.M * c.co, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        float v = c.partial[e];
+        for (int z = 1; z < c.splits; ++z) v += c.partial[(int64_t)z * total + e];
+        const int m = (int)(e / c.co), co = (int)(e - (int64_t)m * c.co);
+        emit<X3>(c, m, co, v);
+    }
+}
+
+// w' and b' of FrozenBatchNorm2d folded into the conv; planes [pl][co][kpad], zero past K
+__global__ void __launch_bounds__(256) backbone_pack_kernel(const float *w, const float *gamma, const float *beta,
+                                                            const float *mean, const float *var, float eps, int co, int ci,
+                                                            int ks, int kpad, int layout, int precision, uint16_t *out,
+                                                            float *bias)
+{
+    const int kk2 = ks * ks, K = ci * kk2;
+    const int64_t total = (int64_t)co * kpad, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int o = (int)(e / kpad), k = (int)(e - (int64_t)o * kpad);
+        const float s = gamma[o] / sqrtf(var[o] + eps);
+        float v = 0.f;
+        if (k < K) {
+            int64_t src;
+            if (layout == 0) {   // k = tap * ci + c
+                const int tap = k / ci, cc = k - tap * ci;
+                src = ((int64_t)o * ci + cc) * kk2 + tap;
+            } else {
+                src = (int64_t)o * K + k;
+            }
+            v = w[src] * s;
+        }
+        if (k == 0) bias[o] = beta[o] - mean[o] * s;
+        if (precision == 0) {
+            const float r1 = v - __uint_as_float(__float_as_uint(v) & 0xffff0000u);
+            const float r2 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
+            out[e] = (uint16_t)(__float_as_uint(v) >> 16);
+            out[total + e] = (uint16_t)(__float_as_uint(r1) >> 16);
+            out[2 * total + e] = (uint16_t)(__float_as_uint(r2) >> 16);
+        } else {
+            out[e] = (uint16_t)f32_to_act_bits(v);
+        }
+    }
+}
+
+// 16 bytes (4 fp32 | 8 16-bit channels) of one output pixel per thread; padding taps never win (PyTorch's -inf)
+template <bool X3>
+__global__ void __launch_bounds__(256) backbone_maxpool_kernel(const char *x, int batch, int h, int w, int c, int ho, int wo,
+                                                               char *out)
+{
+    constexpr int per = X3 ? 4 : 8;
+    const int vec = c / per;
+    const int64_t total = (int64_t)batch * ho * wo * vec, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int v = (int)(e % vec);
+        const int64_t pix = e / vec;
+        const int ox = (int)(pix % wo), oy = (int)((pix / wo) % ho), n = (int)(pix / ((int64_t)wo * ho));
+        float mx[per];
+#pragma unroll
+        for (int i = 0; i < per; ++i) mx[i] = -INFINITY;
+        for (int dy = 0; dy < 3; ++dy) {
+            const int iy = 2 * oy - 1 + dy;
+            if (iy < 0 || iy >= h) continue;
+            for (int dx = 0; dx < 3; ++dx) {
+                const int ix = 2 * ox - 1 + dx;
+                if (ix < 0 || ix >= w) continue;
+                const uint4 q = *reinterpret_cast<const uint4 *>(x + ((((int64_t)n * h + iy) * w + ix) * c + v * per) *
+                                                                         (X3 ? 4 : 2));
+                const uint32_t u[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (X3) {
+                        mx[i] = fmaxf(mx[i], __uint_as_float(u[i]));
+                    } else {
+                        mx[2 * i] = fmaxf(mx[2 * i], act_lo(u[i]));
+                        mx[2 * i + 1] = fmaxf(mx[2 * i + 1], act_hi(u[i]));
+                    }
+                }
+            }
+        }
+        uint4 r;
+        if (X3) r = make_uint4(__float_as_uint(mx[0]), __float_as_uint(mx[1]), __float_as_uint(mx[2]), __float_as_uint(mx[3]));
+        else r = make_uint4(pack_act2(mx[0], mx[1]), pack_act2(mx[2], mx[3]), pack_act2(mx[4], mx[5]), pack_act2(mx[6], mx[7]));
+        *reinterpret_cast<uint4 *>(out + e * 16) = r;
+    }
+}
+
+struct BatchArgs {
+    const void *img[kBMaxImages];
+    int h[kBMaxImages], w[kBMaxImages];
+    int batch, hp, wp, is_u8;
+    float *canvas;
+    uint8_t *mask;
+};
+
+// canvas[b, ch, y, x] = (v - mean[ch]) / std[ch] inside image b (v = u8 / 255 for uint8 input), 0 on padding
+__global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
+{
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
+    const int64_t plane = (int64_t)a.hp * a.wp, total = a.batch * plane, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int b = (int)(e / plane);
+        const int64_t p = e - b * plane;
+        const int y = (int)(p / a.wp), x = (int)(p - (int64_t)y * a.wp);
+        const int h = a.h[b], w = a.w[b];
+        const bool in = y < h && x < w;
+        for (int ch = 0; ch < 3; ++ch) {
+            float v = 0.f;
+            if (in) {
+                const int64_t src = ((int64_t)ch * h + y) * w + x;
+                const float raw = a.is_u8 ? (float)reinterpret_cast<const uint8_t *>(a.img[b])[src] / 255.f
+                                          : reinterpret_cast<const float *>(a.img[b])[src];
+                v = (raw - mean[ch]) / sd[ch];
+            }
+            a.canvas[((int64_t)b * 3 + ch) * plane + p] = v;
+        }
+        a.mask[e] = in ? 0 : 1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ host
+int out_hw(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+int round32(int v) { return (v + 31) / 32 * 32; }
+
+int resolve_splits(int M, int co, int kpad, int requested)
+{
+    const int steps = kpad / kBK;
+    if (requested > 0) return std::max(1, std::min(requested, steps));
+    const int tiles = ((M + kBM - 1) / kBM) * ((co + kBN - 1) / kBN);
+    if (tiles >= 192) return 1;
+    return std::max(1, std::min({8, 256 / tiles, steps / 4}));
+}
+
+// validated kernel arguments of one conv op (precision 0 fp32, 1 the library's 16-bit type)
+int make_conv(const char *what, const sdetr_backbone_op &o, int precision, BConv &c)
+{
+    if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
+    if (!o.x || !o.weight || !o.bias || !o.out) return fail("%s: null tensor", what);
+    if (o.batch < 1 || o.in_channels < 1 || o.out_channels < 1 || o.height < 1 || o.width < 1)
+        return fail("%s: bad shape (batch %d, in %d, out %d, %d x %d)", what, o.batch, o.in_channels, o.out_channels,
+                    o.height, o.width);
+    if (o.kernel_size < 1 || o.kernel_size > 7 || o.stride < 1 || o.stride > 2 || o.padding < 0 ||
+        o.padding >= o.kernel_size)
+        return fail("%s: unsupported kernel %d / stride %d / padding %d", what, o.kernel_size, o.stride, o.padding);
+    if (o.x_nchw == 0 && o.in_channels % 32)
+        return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
+    if ((reinterpret_cast<uintptr_t>(o.x) | reinterpret_cast<uintptr_t>(o.weight)) & 15)
+        return fail("%s: x and weight must be 16-byte aligned", what);
+    c.x = reinterpret_cast<const char *>(o.x);
+    c.w = reinterpret_cast<const uint16_t *>(o.weight);
+    c.bias = o.bias;
+    c.res = reinterpret_cast<const char *>(o.residual);
+    c.out = reinterpret_cast<char *>(o.out);
+    c.out_nchw = o.out_nchw;
+    c.partial = nullptr;
+    c.batch = o.batch;
+    c.ci = o.in_channels;
+    c.h = o.height;
+    c.w_in = o.width;
+    c.co = o.out_channels;
+    c.ks = o.kernel_size;
+    c.stride = o.stride;
+    c.pad = o.padding;
+    c.ho = out_hw(o.height, o.kernel_size, o.stride, o.padding);
+    c.wo = out_hw(o.width, o.kernel_size, o.stride, o.padding);
+    if (c.ho < 1 || c.wo < 1) return fail("%s: empty output", what);
+    c.relu = o.relu ? 1 : 0;
+    c.K = o.in_channels * o.kernel_size * o.kernel_size;
+    c.kpad = round32(c.K);
+    const int64_t M = (int64_t)o.batch * c.ho * c.wo;
+    const int64_t esz = (o.x_nchw || precision == 0) ? 4 : 2;
+    const int64_t x_bytes = (int64_t)o.batch * o.in_channels * o.height * o.width * esz;
+    const int64_t w_bytes = (int64_t)(precision == 0 ? 3 : 1) * o.out_channels * c.kpad * 2;
+    if (M >= (1 << 30) || x_bytes >= (int64_t(1) << 31) || w_bytes >= (int64_t(1) << 31) ||
+        M * o.out_channels >= (int64_t(1) << 31))
+        return fail("%s: tensors too large for 32-bit offsets", what);
+    c.M = (int)M;
+    c.x_bytes = (uint32_t)x_bytes;
+    c.w_bytes = (uint32_t)w_bytes;
+    c.plane = (int64_t)o.out_channels * c.kpad;
+    c.splits = resolve_splits(c.M, c.co, c.kpad, o.splits);
+    c.k_per_split = (c.kpad / kBK + c.splits - 1) / c.splits * kBK;
+    c.splits = (c.kpad + c.k_per_split - 1) / c.k_per_split;
+    return 0;
+}
+
+int64_t conv_workspace(const BConv &c) { return c.splits > 1 ? (int64_t)c.splits * c.M * c.co * 4 : 0; }
+
+template <bool X3, bool NCHW>
+void launch_conv(hipStream_t s, const BConv &c)
+{
+    static DeviceOnce once;
+    allow_dynamic_lds(backbone_conv_kernel<X3, NCHW>, once, BCfg<X3>::kLds);
+    const dim3 grid((unsigned)((c.M + kBM - 1) / kBM), (unsigned)((c.co + kBN - 1) / kBN), (unsigned)c.splits);
+    hipLaunchKernelGGL((backbone_conv_kernel<X3, NCHW>), grid, dim3(kBThreads), BCfg<X3>::kLds, s, c);
+}
+
+int run_conv(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws, int64_t ws_bytes)
+{
+    BConv c;
+    if (int rc = make_conv("sdetr_backbone_conv", o, precision, c)) return rc;
+    if (conv_workspace(c) > ws_bytes || (conv_workspace(c) && !ws))
+        return fail("sdetr_backbone_conv: workspace of %lld bytes is too small (%lld needed)", (long long)ws_bytes,
+                    (long long)conv_workspace(c));
+    c.partial = reinterpret_cast<float *>(ws);
+    const bool x3 = precision == 0;
+    if (x3 && o.x_nchw) launch_conv<true, true>(s, c);
+    else if (x3) launch_conv<true, false>(s, c);
+    else if (o.x_nchw) launch_conv<false, true>(s, c);
+    else launch_conv<false, false>(s, c);
+    if (c.splits > 1) {
+        const int64_t total = (int64_t)c.M * c.co;
+        const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+        if (x3) hipLaunchKernelGGL(backbone_splitk_kernel<true>, dim3(blocks), dim3(256), 0, s, c);
+        else hipLaunchKernelGGL(backbone_splitk_kernel<false>, dim3(blocks), dim3(256), 0, s, c);
+    }
+    return check_launch("sdetr_backbone_conv");
+}
+
+int run_maxpool(hipStream_t s, const void *x, int batch, int h, int w, int c, int precision, void *out)
+{
+    if (precision != 0 && precision != 1) return fail("sdetr_backbone_maxpool: precision must be 0 or 1");
+    if (!x || !out) return fail("sdetr_backbone_maxpool: null tensor");
+    if (batch < 1 || h < 1 || w < 1 || c < 1 || c % 8)
+        return fail("sdetr_backbone_maxpool: bad shape (batch %d, %d x %d, channels %d: a multiple of 8)", batch, h, w, c);
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15)
+        return fail("sdetr_backbone_maxpool: tensors must be 16-byte aligned");
+    const int ho = out_hw(h, 3, 2, 1), wo = out_hw(w, 3, 2, 1);
+    const int64_t total = (int64_t)batch * ho * wo * (c / (precision == 0 ? 4 : 8));
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+    if (precision == 0)
+        hipLaunchKernelGGL(backbone_maxpool_kernel<true>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const char *>(x),
+                           batch, h, w, c, ho, wo, reinterpret_cast<char *>(out));
+    else
+        hipLaunchKernelGGL(backbone_maxpool_kernel<false>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const char *>(x),
+                           batch, h, w, c, ho, wo, reinterpret_cast<char *>(out));
+    return check_launch("sdetr_backbone_maxpool");
+}
+
+}  // namespace
+}  // namespace sdetr
+
+using namespace sdetr;
+
+extern "C" int64_t sdetr_backbone_packed_bytes(int out_channels, int in_channels, int kernel_size, int precision)
+{
+    if (out_channels < 1 || in_channels < 1 || kernel_size < 1 || (precision != 0 && precision != 1)) return -1;
+    return (int64_t)(precision == 0 ? 3 : 1) * out_channels * round32(in_channels * kernel_size * kernel_size) * 2;
+}
+
+extern "C" int sdetr_backbone_pack(sdetr_stream_t stream, const float *weight, const float *gamma, const float *beta,
+                                   const float *running_mean, const float *running_var, float eps, int out_channels,
+                                   int in_channels, int kernel_size, int layout, int precision, void *packed, float *bias)
+{
+    if (!weight || !gamma || !beta || !running_mean || !running_var || !packed || !bias)
+        return fail("sdetr_backbone_pack: null tensor");
+    if (sdetr_backbone_packed_bytes(out_channels, in_channels, kernel_size, precision) < 0 || (layout != 0 && layout != 1))
+        return fail("sdetr_backbone_pack: bad arguments (out %d, in %d, kernel %d, layout %d, precision %d)", out_channels,
+                    in_channels, kernel_size, layout, precision);
+    const int kpad = round32(in_channels * kernel_size * kernel_size);
+    const int64_t total = (int64_t)out_channels * kpad;
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(backbone_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, weight, gamma, beta,
+                       running_mean, running_var, eps, out_channels, in_channels, kernel_size, kpad, layout, precision,
+                       reinterpret_cast<uint16_t *>(packed), bias);
+    return check_launch("sdetr_backbone_pack");
+}
+
+extern "C" int sdetr_backbone_conv_splits(const sdetr_backbone_op *op, int precision)
+{
+    BConv c;
+    if (!op || op->op != 0) return fail("sdetr_backbone_conv_splits: not a conv op");
+    if (make_conv("sdetr_backbone_conv_splits", *op, precision, c)) return SDETR_EINVAL;
+    return c.splits;
+}
+
+extern "C" int64_t sdetr_backbone_workspace_bytes(const sdetr_backbone_op *ops, int n_ops, int precision)
+{
+    if (!ops || n_ops < 1) return -1;
+    int64_t need = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        if (ops[i].op != 0) continue;
+        BConv c;
+        if (make_conv("sdetr_backbone_workspace_bytes", ops[i], precision, c)) return -1;
+        need = std::max(need, conv_workspace(c));
+    }
+    return need;
+}
+
+extern "C" int sdetr_backbone_conv(sdetr_stream_t stream, const sdetr_backbone_op *op, int precision, void *workspace,
+                                   int64_t workspace_bytes)
+{
+    if (!op || op->op != 0) return fail("sdetr_backbone_conv: not a conv op");
+    return run_conv((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
+}
+
+extern "C" int sdetr_backbone_maxpool(sdetr_stream_t stream, const void *x, int batch, int height, int width, int channels,
+                                      int precision, void *out)
+{
+    return run_maxpool((hipStream_t)stream, x, batch, height, width, channels, precision, out);
+}
+
+extern "C" int sdetr_backbone_run(sdetr_stream_t stream, const sdetr_backbone_op *ops, int n_ops, int precision,
+                                  void *workspace, int64_t workspace_bytes)
+{
+    if (!ops || n_ops < 1) return fail("sdetr_backbone_run: empty plan");
+    // validate the whole plan before the first launch
+    for (int i = 0; i < n_ops; ++i) {
+        BConv c;
+        if (ops[i].op == 0) {
+            if (make_conv("sdetr_backbone_run", ops[i], precision, c)) return SDETR_EINVAL;
+            if (conv_workspace(c) > workspace_bytes || (conv_workspace(c) && !workspace))
+                return fail("sdetr_backbone_run: op %d needs %lld workspace bytes", i, (long long)conv_workspace(c));
+        } else if (ops[i].op != 1) {
+            return fail("sdetr_backbone_run: op %d has unknown kind %d", i, ops[i].op);
+        }
+    }
+    for (int i = 0; i < n_ops; ++i) {
+        const sdetr_backbone_op &o = ops[i];
+        const int rc = o.op == 0 ? run_conv((hipStream_t)stream, o, precision, workspace, workspace_bytes)
+                                 : run_maxpool((hipStream_t)stream, o.x, o.batch, o.height, o.width, o.in_channels,
+                                               precision, o.out);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
+                                           int is_uint8, int canvas_height, int canvas_width, float *canvas, uint8_t *mask)
+{
+    if (!images || !image_hw || !canvas || !mask) return fail("sdetr_backbone_batch_images: null argument");
+    if (batch < 1 || batch > kBMaxImages) return fail("sdetr_backbone_batch_images: 1 .. %d images (got %d)", kBMaxImages, batch);
+    BatchArgs a;
+    for (int b = 0; b < batch; ++b) {
+        const int h = image_hw[2 * b], w = image_hw[2 * b + 1];
+        if (!images[b] || h < 1 || w < 1 || h > canvas_height || w > canvas_width)
+            return fail("sdetr_backbone_batch_images: image %d (%d x %d) does not fit the %d x %d canvas", b, h, w,
+                        canvas_height, canvas_width);
+        a.img[b] = images[b];
+        a.h[b] = h;
+        a.w[b] = w;
+    }
+    a.batch = batch;
+    a.hp = canvas_height;
+    a.wp = canvas_width;
+    a.is_u8 = is_uint8 ? 1 : 0;
+    a.canvas = canvas;
+    a.mask = mask;
+    const int64_t total = (int64_t)batch * canvas_height * canvas_width;
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(backbone_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("sdetr_backbone_batch_images");
+}
