@@ -1225,7 +1225,9 @@ int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, i
  * sdetr_backbone_batch_images: images = host array of `batch` device pointers to [3, h_i, w_i] (f32 in [0, 1], or u8
  * when is_uint8: v / 255), image_hw host int [batch][2]; canvas f32 [batch, 3, canvas_height, canvas_width] =
  * (v - mean[c]) / std[c] (ImageNet mean 0.485 0.456 0.406, std 0.229 0.224 0.225) inside image b, 0 on padding; mask
- * u8 [batch, canvas_height, canvas_width] = 1 on padding.  At most 64 images.
+ * u8 [batch, canvas_height, canvas_width] = 1 on padding.  At most 64 images.  sdetr_backbone_batch_images_ex: the same
+ * launch with a `normalize` switch; 0 copies the values as they are (training: images arrive normalised), so the canvas
+ * equals the inputs bit for bit inside every image.
  * --------------------------------------------------------------------------------------------- */
 typedef struct sdetr_backbone_op {
     int op;
@@ -1262,6 +1264,38 @@ int sdetr_backbone_run(sdetr_stream_t stream, const sdetr_backbone_op *ops, int 
                        int64_t workspace_bytes);
 int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
                                 int is_uint8, int canvas_height, int canvas_width, float *canvas, uint8_t *mask);
+int sdetr_backbone_batch_images_ex(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
+                                   int is_uint8, int normalize, int canvas_height, int canvas_width, float *canvas,
+                                   uint8_t *mask);
+
+/* ---------------------------------------------------------------------------------------------
+ * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.
+ *
+ * sdetr_cdn_queries: ONE launch.  boxes f32 [batch * capacity, 4] (cx, cy, w, h in [0, 1]), labels int32
+ * [batch * capacity], offsets int32 [batch + 1]: the staged targets of sdetr_set_match / sdetr_set_loss.  weight f32
+ * [num_classes, embed_dim] (label_encoder.weight).  noise f32 [2 * groups, batch * capacity, 10], uniforms in [0, 1) per
+ * (repeat r, staged row): column 0 flips the label when below label_noise_prob * 0.5, column 1 is the new label as
+ * floor(u * num_classes) clipped to num_classes - 1, columns 2-5 the signs (u >= 0.5: +1), columns 6-9 the magnitudes
+ * (may be NULL when label_noise_prob <= 0 and box_noise_scale <= 0).  With n_dn = 2 * groups * max_gt, target t of image b
+ * in repeat r (even: positive copy of group r / 2, odd: negative) goes to slot r * max_gt + t:
+ *   label_queries f32 [batch, n_dn, embed_dim] = weight[label'] (a plain copy); box_queries f32 [batch, n_dn, 4] = the
+ *   noised box in inverse-sigmoid space (eps 1e-3); noised_labels int32 [batch, n_dn] = label', -1 on padding slots
+ *   (t >= the image's count; their label and box rows are written as zeros; so are slots whose label lies outside
+ *   [0, num_classes)); attn_mask u8 (bool) [n_dn + num_queries]^2, 1 = may not attend: allowed(i, j) iff j >= n_dn, or
+ *   i < n_dn and i, j in the same block of 2 * max_gt slots.
+ * Every output element is written by the launch.  max_gt in [1, capacity], groups >= 1, embed_dim a multiple of 4,
+ * n_dn + num_queries <= 46340; boxes, weight, label_queries, box_queries, attn_mask 16-byte aligned.
+ *
+ * sdetr_cdn_label_grad: ONE launch, one workgroup per class; grad_weight f32 [num_classes, embed_dim], row c = the sum
+ * of grad_label_queries [batch, n_dn, embed_dim] rows whose noised_labels entry is c, added in slot order (no atomics:
+ * bit-identical from run to run), zeros for absent classes.  Every element of grad_weight is written.
+ * --------------------------------------------------------------------------------------------- */
+int sdetr_cdn_queries(sdetr_stream_t stream, const float *boxes, const int *labels, const int *offsets, int capacity,
+                      const float *weight, const float *noise, int batch, int max_gt, int groups, int num_classes,
+                      int embed_dim, int num_queries, float label_noise_prob, float box_noise_scale, float *label_queries,
+                      float *box_queries, int *noised_labels, uint8_t *attn_mask);
+int sdetr_cdn_label_grad(sdetr_stream_t stream, const float *grad_label_queries, const int *noised_labels, int batch,
+                         int n_dn, int num_classes, int embed_dim, float *grad_weight);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,11 @@
+"""Salience-DETR on MI355X.  Modules are imported by name (``salience_detr_amd.detector`` ...); the training-side entry
+points are also reachable from the package, resolved on first use so that importing the package stays free of torch."""
+
+_LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "SalienceDETRHead": "detector"}
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        from importlib import import_module
+        return getattr(import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -422,16 +422,20 @@ class ResNetBackbone(nn.Module):
         return outputs
 
 
-def batch_images(images: Sequence[Tensor], size_divisible: int = 32) -> Tuple[Tensor, Tensor]:
+def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: bool = True) -> Tuple[Tensor, Tensor]:
     """ONE launch: ``images`` ``[3, h_i, w_i]`` (float in [0, 1], or uint8 read as ``v / 255``) normalised with the
     ImageNet mean / std and padded with 0 after normalisation into ``canvas`` ``[B, 3, Hp, Wp]`` (Hp, Wp = the largest
     size rounded up to ``size_divisible``) and ``mask`` ``[B, Hp, Wp]`` (bool, True on padding): the reference's eval
-    ``ConvertImageDtype`` + ``Normalize`` + ``image_list_from_tensors`` + ``construct_mask``."""
+    ``ConvertImageDtype`` + ``Normalize`` + ``image_list_from_tensors`` + ``construct_mask``.  ``normalize=False`` (the
+    reference's training mode, whose images arrive normalised from the dataset transforms: float32 only) only pads and
+    builds the mask: the canvas equals the inputs bit for bit inside every image."""
     if len(images) == 0:
         raise ValueError("batch_images: no images")
     dev, dt = images[0].device, images[0].dtype
     if dt not in (torch.float32, torch.uint8):
         raise RuntimeError(f"batch_images: images must be float32 or uint8, got {dt}")
+    if not normalize and dt != torch.float32:
+        raise RuntimeError(f"batch_images: normalize=False takes float32 images only, got {dt}")
     for im in images:
         if im.dim() != 3 or im.shape[0] != 3 or im.dtype != dt or im.device != dev:
             raise RuntimeError("batch_images: every image must be [3, h, w] of one dtype on one device")
@@ -443,6 +447,7 @@ def batch_images(images: Sequence[Tensor], size_divisible: int = 32) -> Tuple[Te
     ptrs = (ctypes.c_void_p * len(images))(*[im.data_ptr() for im in images])
     hw = (ctypes.c_int * (2 * len(images)))(*[int(v) for im in images for v in im.shape[1:]])
     lib = _hip.lib()
-    _hip.check(lib.sdetr_backbone_batch_images(_hip.stream_ptr(), ptrs, hw, len(images), 1 if dt == torch.uint8 else 0, hp,
-                                               wp, canvas.data_ptr(), mask.data_ptr()), "batch_images", lib)
+    _hip.check(lib.sdetr_backbone_batch_images_ex(_hip.stream_ptr(), ptrs, hw, len(images), 1 if dt == torch.uint8 else 0,
+                                                  1 if normalize else 0, hp, wp, canvas.data_ptr(), mask.data_ptr()),
+               "batch_images", lib)
     return canvas, mask

@@ -420,12 +420,13 @@ __global__ void __launch_bounds__(256) backbone_maxpool_kernel(const char *x, in
 struct BatchArgs {
     const void *img[kBMaxImages];
     int h[kBMaxImages], w[kBMaxImages];
-    int batch, hp, wp, is_u8;
+    int batch, hp, wp, is_u8, normalize;
     float *canvas;
     uint8_t *mask;
 };
 
-// canvas[b, ch, y, x] = (v - mean[ch]) / std[ch] inside image b (v = u8 / 255 for uint8 input), 0 on padding
+// canvas[b, ch, y, x] = (v - mean[ch]) / std[ch] inside image b (v = u8 / 255 for uint8 input), 0 on padding; without
+// `normalize` the value itself (bit for bit)
 __global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
 {
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
@@ -442,7 +443,7 @@ __global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
                 const int64_t src = ((int64_t)ch * h + y) * w + x;
                 const float raw = a.is_u8 ? (float)reinterpret_cast<const uint8_t *>(a.img[b])[src] / 255.f
                                           : reinterpret_cast<const float *>(a.img[b])[src];
-                v = (raw - mean[ch]) / sd[ch];
+                v = a.normalize ? (raw - mean[ch]) / sd[ch] : raw;
             }
             a.canvas[((int64_t)b * 3 + ch) * plane + p] = v;
         }
@@ -657,8 +658,9 @@ extern "C" int sdetr_backbone_run(sdetr_stream_t stream, const sdetr_backbone_op
     return 0;
 }
 
-extern "C" int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
-                                           int is_uint8, int canvas_height, int canvas_width, float *canvas, uint8_t *mask)
+extern "C" int sdetr_backbone_batch_images_ex(sdetr_stream_t stream, const void *const *images, const int *image_hw,
+                                              int batch, int is_uint8, int normalize, int canvas_height, int canvas_width,
+                                              float *canvas, uint8_t *mask)
 {
     if (!images || !image_hw || !canvas || !mask) return fail("sdetr_backbone_batch_images: null argument");
     if (batch < 1 || batch > kBMaxImages) return fail("sdetr_backbone_batch_images: 1 .. %d images (got %d)", kBMaxImages, batch);
@@ -676,10 +678,18 @@ extern "C" int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *co
     a.hp = canvas_height;
     a.wp = canvas_width;
     a.is_u8 = is_uint8 ? 1 : 0;
+    a.normalize = normalize ? 1 : 0;
     a.canvas = canvas;
     a.mask = mask;
     const int64_t total = (int64_t)batch * canvas_height * canvas_width;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(backbone_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("sdetr_backbone_batch_images");
+}
+
+extern "C" int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
+                                           int is_uint8, int canvas_height, int canvas_width, float *canvas, uint8_t *mask)
+{
+    return sdetr_backbone_batch_images_ex(stream, images, image_hw, batch, is_uint8, 1, canvas_height, canvas_width, canvas,
+                                          mask);
 }
