@@ -1,4 +1,5 @@
-"""Generate tests/golden/detector_train_small.npz from the IMPORTED reference ``SalienceDETR`` in ``train()`` mode.
+"""Generate tests/golden/detector_train_<tag>.npz from the IMPORTED reference ``SalienceDETR`` in ``train()`` mode: one
+training step (forward, ``sum(losses.values()).backward()``) per target layout.
 
 Run in the authoring container only (needs the upstream reference checkout and scipy, see _ref_import.py):
 
@@ -16,10 +17,24 @@ plumbing-level: torchvision's box functions (make_set_criterion_golden.py, make_
 ``Normalize`` only exist in the eval transform, which training does not apply: identities), and the padding helper
 ``image_list_from_tensors`` (zero padding to a multiple of 32 + the image sizes; the stub backbone ignores pixel values).
 
+Cases (``CASES``): ``small`` counts (3, 2); ``empty_first`` counts (0, 4), an image without targets in a batch that has
+some; ``groups_one`` counts (5, 1) at ``denoising_nums = 3``, where ``denoising_groups`` takes its floor of one group.
 Inputs are redrawn until the proposal stage keeps ten tokens per image and scipy's assignment of every (output, image)
 problem is unchanged under 1e-5 relative noise on the cost (make_set_criterion_golden.stable), so that the Hungarian
-optimum is unique with margin.  The file holds the stored maps, the targets (xyxy pixels), the recorded draws, the
-state-dict key list with checksums (weights are name-seeded: ``synthetic.det_state_dict``) and the weighted loss dict.
+optimum is unique with margin.  The reference ran all three layouts as they are.
+
+Expected gradients come from a SECOND step of the same reference detector in float64 on the same fp32-drawn maps,
+targets, weights and recorded draws, cast up (``torch.set_default_dtype(torch.float64)`` gets the reference past its
+hard-coded float tensors).  Both steps must pick the same indices wherever the model picks any -- every top-k, sort,
+NMS survivor set and Hungarian assignment is recorded and compared (``Decisions``) -- or the script stops.
+
+A file holds the stored maps, the targets (xyxy pixels), the recorded draws, the state-dict key list with checksums
+(weights are name-seeded: ``synthetic.det_state_dict``), the weighted loss dict of the fp32 step (``loss_values``) and of
+the float64 step, and of the float64 step's gradients: those of the stored maps in full and of a spread of parameters
+(``grad_names``; matrices above ``sub_above`` elements as ``[::sub_step, ::sub_step]``) as ``grad.<name>`` with their
+``grad_max``; the L2 norm of every parameter's gradient (``norm_names`` / ``grad_norms``); and per stored tensor and per
+norm the distance of the fp32 step from the float64 one, ``grad_d_ref = max|g32 - g64| / max|g64|`` and ``norm_d_ref``,
+the scale of the test's bars.  A rerun may not change the ``PINNED`` keys of a committed file.
 """
 import os
 import sys
@@ -68,9 +83,15 @@ base_detector.T.Normalize = lambda *a, **k: nn.Identity()
 from models.detectors.salience_detr import SalienceCriterion, SalienceDETR  # noqa: E402
 
 SALT = 9
-DENOISING_NUMS = 12
-COUNTS = (3, 2)
 BACKBONE_CHANNELS = (32, 64, 64)
+SUB_ABOVE = 4096        # gradients with more elements are stored as [::4, ::4]
+# tag (detector_train_<tag>.npz), targets per image, denoising_nums, seed
+CASES = [("small", (3, 2), 12, 20261018),
+         ("empty_first", (0, 4), 12, 20261101),     # an image without targets next to one with four
+         ("groups_one", (5, 1), 3, 20261102)]       # more targets than denoising_nums: one denoising group, its floor
+# what a rerun may not change in a committed file: the inputs, the recorded draws and the fp32 loss values
+PINNED = ("image_sizes", "counts", "salt", "denoising_nums", "tboxes", "tlabels", "draw_flip", "draw_label", "draw_sign",
+          "draw_magnitude", "sd_keys", "sd_crc", "loss_keys", "loss_values", "map0", "map1", "map2")
 
 
 class StoredBackbone(nn.Module):
@@ -94,7 +115,7 @@ def weight_dict(dec_layers):
     return w
 
 
-def build(maps):
+def build(maps, denoising_nums, sd=None):
     c = MG.TRANSFORMER_SMALL
     E, heads = c["E"], c["heads"]
     enc_layer = MG.SalienceTransformerEncoderLayer(embed_dim=E, d_ffn=c["d_ffn"], dropout=0.0, n_heads=heads,
@@ -112,18 +133,22 @@ def build(maps):
     det = SalienceDETR(StoredBackbone(maps), ChannelMapper(list(BACKBONE_CHANNELS), E, 4),
                        MG.PositionEmbeddingSine(E // 2, temperature=10000, normalize=True, offset=-0.5), tr, crit,
                        nn.Identity(), SalienceCriterion(noise_scale=0.0), num_classes=c["classes"],
-                       num_queries=c["proposals"], denoising_nums=DENOISING_NUMS, aux_loss=True)
-    sd = syn.det_state_dict(det.state_dict(), salt=SALT)
+                       num_queries=c["proposals"], denoising_nums=denoising_nums, aux_loss=True)
+    # (the deformable attention's init_weights replaces a bias by a hard-coded float32 parameter: under a float64
+    # default dtype this cast brings it along; under float32 it does nothing)
+    det = det.to(torch.get_default_dtype())
+    if sd is None:
+        sd = syn.det_state_dict(det.state_dict(), salt=SALT)
     det.load_state_dict(sd)
     return det.train(), sd
 
 
-def draw(g):
+def draw(g, counts):
     sizes = MG.TRANSFORMER_SMALL["image_sizes"]
     hp, wp = 64, 96
     maps = [torch.randn(len(sizes), ch, hp // s, wp // s, generator=g) for ch, s in zip(BACKBONE_CHANNELS, (8, 16, 32))]
     targets = []
-    for n, (h, w) in zip(COUNTS, sizes):
+    for n, (h, w) in zip(counts, sizes):
         x0 = torch.rand(n, generator=g) * 0.5 * w
         y0 = torch.rand(n, generator=g) * 0.5 * h
         bw = torch.rand(n, generator=g) * 0.4 * w + 4
@@ -133,30 +158,144 @@ def draw(g):
     return maps, targets
 
 
-def main():
-    import torchvision
-    from oracle import salience_ref as R
+class Replayer:
+    """Wraps torch.rand_like / torch.randint_like: hands out recorded draws in order, cast to the dtype asked for."""
+
+    def __init__(self, draws):
+        self.draws, self.at = draws, 0
+
+    def _next(self, kind, x, kw):
+        k, d = self.draws[self.at]
+        self.at += 1
+        assert k == kind and d.shape == x.shape, (self.at, k, kind, tuple(d.shape), tuple(x.shape))
+        return d.to(kw.get("dtype", x.dtype))
+
+    def __enter__(self):
+        self._rand_like, self._randint_like = torch.rand_like, torch.randint_like
+        torch.rand_like = lambda x, **kw: self._next("rand", x, kw)
+        torch.randint_like = lambda x, low=0, high=None, **kw: self._next("randint", x, kw)
+        return self
+
+    def __exit__(self, *exc):
+        torch.rand_like, torch.randint_like = self._rand_like, self._randint_like
+        assert exc[0] is not None or self.at == len(self.draws)
+
+
+class Decisions:
+    """Keeps every index a forward pass picks -- top-k (level / layer token selection, proposals, the encoder's
+    ``topk_sa``), sort, NMS survivors, Hungarian assignments -- so that two passes can be held to the same ones."""
+
+    def __init__(self, det):
+        self.det, self.log = det, []
+
+    def __enter__(self):
+        import torchvision
+        from oracle import salience_ref as R
+        self._topk, self._sort, self._match = torch.topk, torch.sort, self.det.criterion.matcher.forward
+
+        def topk(*a, **k):
+            out = self._topk(*a, **k)
+            self.log.append(("topk", out[1].sort(-1)[0].clone()))
+            return out
+
+        def sort(*a, **k):
+            out = self._sort(*a, **k)
+            self.log.append(("sort", out[1].clone()))
+            return out
+
+        def nms(boxes, scores, idxs, thr):
+            keep = R.batched_nms(boxes, scores, idxs, thr)
+            self.log.append(("nms", keep.sort()[0].clone()))
+            return keep
+
+        def match(*a, **k):
+            out = self._match(*a, **k)
+            self.log.append(("match", torch.stack([torch.as_tensor(v) for v in out])))     # one image: (rows, columns)
+            return out
+
+        torch.topk, torch.sort, torch.Tensor.topk = topk, sort, lambda x, *a, **k: topk(x, *a, **k)
+        torchvision.ops.batched_nms, self.det.criterion.matcher.forward = nms, match
+        return self
+
+    def __exit__(self, *exc):
+        import torchvision
+        torch.topk, torch.sort = self._topk, self._sort
+        del torch.Tensor.topk
+        torchvision.ops.batched_nms, self.det.criterion.matcher.forward = None, self._match
+
+    def same(self, other):
+        return len(self.log) == len(other.log) and all(
+            a == b and x.shape == y.shape and torch.equal(x, y) for (a, x), (b, y) in zip(self.log, other.log))
+
+
+def grad_names(enc_layers, dec_layers):
+    """The stored spread: every part the training branch wires together (the file carries the list)."""
+    t = "transformer."
+    names = ["denoising_generator.label_encoder.weight", "neck.convs.0.0.weight", "neck.convs.2.0.weight",
+             "neck.convs.3.0.weight", "neck.convs.1.1.weight", "neck.convs.3.1.bias",
+             t + "alpha", t + "level_embeds", t + "tgt_embed.weight", t + "enc_output.weight", t + "enc_output_norm.bias",
+             t + "encoder_class_head.weight", t + "encoder_class_head.bias", t + "encoder_bbox_head.layers.0.weight",
+             t + "encoder_bbox_head.layers.2.bias", t + "enc_mask_predictor.layer1.1.weight",
+             t + "enc_mask_predictor.layer2.4.weight", t + "encoder.background_embedding.row_embed.weight"]
+    for i in range(enc_layers):
+        p = f"{t}encoder.layers.{i}."
+        names += [p + "pre_attention.in_proj_weight", p + "self_attn.sampling_offsets.weight",
+                  p + "self_attn.sampling_offsets.bias", p + "self_attn.attention_weights.weight",
+                  p + "self_attn.value_proj.weight", p + "linear1.weight", p + ("norm2.weight" if i else "norm1.bias")]
+    for i in range(dec_layers):
+        p = f"{t}decoder.layers.{i}."
+        names += [p + "self_attn.in_proj_weight", p + "cross_attn.sampling_offsets.weight",
+                  p + "cross_attn.value_proj.weight", p + "linear2.weight", p + ("norm3.bias" if i else "norm2.weight"),
+                  f"{t}decoder.class_head.{i}.weight", f"{t}decoder.bbox_head.{i}.layers.2.weight"]
+    return names + [t + "decoder.ref_point_head.layers.0.weight"]
+
+
+def sub(g):
+    """A gradient as stored (make_golden.sub's rule): whole when small, every 4th row / column of the big matrices."""
+    return g[::4, ::4] if g.numel() > SUB_ABOVE and g.dim() >= 2 else g
+
+
+def forward_backward(det, images, targets, noise):
+    """One training step of the reference detector; the losses, the picked indices, every gradient (float64 copies)."""
+    seen = {}
+    real_forward = det.criterion.forward
+
+    def spy(outputs, prepared):
+        seen["outputs"], seen["targets"] = outputs, prepared
+        return real_forward(outputs, prepared)
+
+    det.criterion.forward = spy
+    try:
+        with Decisions(det) as dec, noise:
+            losses = det(images, targets)
+    finally:
+        det.criterion.forward = real_forward
+    sum(losses.values()).backward()
+    params = dict(det.named_parameters(remove_duplicate=False))
+    assert all(p.grad is not None for p in params.values())
+    grads = {n: p.grad.detach().double() for n, p in params.items()}
+    grads.update({f"map{i}": m.grad.detach().double() for i, m in enumerate(det.backbone.maps)})
+    return losses, dec, grads, seen
+
+
+def own_scale(a, b):
+    """max|a - b| / max|b| (0 where both vanish)."""
+    d, s = (a - b).abs().max().item(), b.abs().max().item()
+    return d / s if s > 0 else d
+
+
+def run_case(tag, counts, denoising_nums, seed):
     c = MG.TRANSFORMER_SMALL
     sizes = c["image_sizes"]
-    g = torch.Generator().manual_seed(20261018)
-    images = [torch.zeros(3, h, w) for h, w in sizes]
-    torchvision.ops.batched_nms = lambda boxes, scores, idxs, thr: R.batched_nms(boxes, scores, idxs, thr)
+    g = torch.Generator().manual_seed(seed)
     tries = 0
     while True:
         tries += 1
-        maps, targets = draw(g)
-        det, sd = build(maps)
-        seen = {}
-        real_forward = det.criterion.forward
-
-        def spy(outputs, prepared):
-            seen["outputs"], seen["targets"] = outputs, prepared
-            return real_forward(outputs, prepared)
-
-        det.criterion.forward = spy
+        maps, targets = draw(g, counts)
+        det, sd = build([m.requires_grad_(True) for m in maps], denoising_nums)
+        rec = MD.Recorder(g)
         try:
-            with MD.Recorder(g) as rec:
-                losses = det(images, targets)
+            losses, dec, grads, seen = forward_backward(det, [torch.zeros(3, h, w) for h, w in sizes], targets, rec)
         except (RuntimeError, AssertionError, IndexError) as e:     # fewer than ten tokens survived the NMS
             print("redraw:", type(e).__name__, str(e)[:80])
             continue
@@ -167,7 +306,6 @@ def main():
         if MS.stable(det.criterion.matcher, logits, boxes, seen["targets"], False, g):
             break
         print("redraw: an assignment is not unique with margin")
-    torchvision.ops.batched_nms = None
     draws = rec.draws
     # the generator's four draws come first; the salience criterion then draws once per (level, image) and multiplies
     # by noise_scale = 0
@@ -176,8 +314,30 @@ def main():
     flip, new_label, sign, magnitude = [d for _, d in draws[:4]]
     assert ((flip - 0.25).abs() > 1e-6).all()
     assert set(losses) == set(weight_dict(c["dec_layers"]))
-    data = {"image_sizes": np.array(sizes), "counts": np.array(COUNTS), "salt": np.array(SALT),
-            "denoising_nums": np.array(DENOISING_NUMS),
+    max_gt = max(counts)
+    groups = max(denoising_nums * max_gt // max_gt ** 2, 1)
+    assert flip.shape == (2 * groups * sum(counts),), (tuple(flip.shape), groups)
+
+    # the same step in float64 on the same fp32-drawn maps, targets, weights and draws, cast up: the expected values,
+    # and the distance of the reference's own fp32 step from them
+    torch.set_default_dtype(torch.float64)
+    try:
+        det64, _ = build([m.detach().double().requires_grad_(True) for m in maps], denoising_nums, sd)
+        t64 = [{"boxes": t["boxes"].double(), "labels": t["labels"]} for t in targets]
+        losses64, dec64, grads64, _ = forward_backward(det64, [torch.zeros(3, h, w) for h, w in sizes], t64,
+                                                       Replayer(draws))
+    finally:
+        torch.set_default_dtype(torch.float32)
+    assert all(p.dtype == torch.float64 for p in det64.parameters()) and losses64["loss_class"].dtype == torch.float64
+    assert dec.same(dec64), "the float64 step picked other tokens, proposals or assignments than the fp32 step"
+    kinds = [k for k, _ in dec.log]
+    print(tag, "decisions held in float64:", {k: kinds.count(k) for k in sorted(set(kinds))})
+
+    names = grad_names(c["enc_layers"], c["dec_layers"])
+    every = [n for n, _ in det.named_parameters()]
+    assert len(every) == 150 and set(names) <= set(grads)
+    data = {"image_sizes": np.array(sizes), "counts": np.array(counts), "salt": np.array(SALT),
+            "denoising_nums": np.array(denoising_nums),
             "tboxes": torch.cat([t["boxes"] for t in targets]).numpy(),
             "tlabels": torch.cat([t["labels"] for t in targets]).numpy().astype(np.int32),
             "draw_flip": flip.numpy(), "draw_label": new_label.numpy().astype(np.int32),
@@ -187,12 +347,42 @@ def main():
             "loss_keys": np.array(sorted(losses)),
             "loss_values": np.array([losses[k].item() for k in sorted(losses)], dtype=np.float64)}
     for i, m in enumerate(maps):
-        data[f"map{i}"] = m.numpy()
-    out = os.path.join(HERE, "detector_train_small.npz")
-    np.savez_compressed(out, **data)
-    print(out, os.path.getsize(out), "bytes after", tries, "draws")
-    for k in sorted(losses):
-        print(f"  {k:20s} {losses[k].item():.6f}")
+        data[f"map{i}"] = m.detach().numpy()
+    data["groups"] = np.array(groups)
+    data["loss_values64"] = np.array([losses64[k].item() for k in sorted(losses)], dtype=np.float64)
+    data["sub_above"], data["sub_step"] = np.array(SUB_ABOVE), np.array(4)
+    stored = [f"map{i}" for i in range(len(maps))] + names
+    data["grad_names"] = np.array(stored)
+    for n in stored:    # expected values: the float64 step's, kept as float32 (half an ulp, far below any bar here)
+        data[f"grad.{n}"] = sub(grads64[n]).float().numpy()
+    data["grad_max"] = np.array([sub(grads64[n]).abs().max().item() for n in stored])
+    data["grad_d_ref"] = np.array([own_scale(sub(grads[n]), sub(grads64[n])) for n in stored])
+    data["norm_names"] = np.array(every)
+    n32 = np.array([grads[n].norm().item() for n in every])
+    data["grad_norms"] = np.array([grads64[n].norm().item() for n in every])
+    data["norm_d_ref"] = np.abs(n32 - data["grad_norms"]) / np.where(data["grad_norms"] > 0, data["grad_norms"], 1.0)
+    assert all(np.isfinite(v).all() for k, v in data.items() if v.dtype.kind == "f")
+    print(tag, "tries", tries, "groups", groups, "zero-gradient parameters",
+          [n for n, v in zip(every, data["grad_norms"]) if v == 0])
+    for n, m, d in zip(stored, data["grad_max"], data["grad_d_ref"]):
+        print(f"  {n:70s} max|g| {m:.3e}  d_ref {d:.2e}")
+    print("  worst norm d_ref", every[int(data["norm_d_ref"].argmax())], data["norm_d_ref"].max())
+    return data, losses
+
+
+def main():
+    for tag, counts, denoising_nums, seed in CASES:
+        data, losses = run_case(tag, counts, denoising_nums, seed)
+        out = os.path.join(HERE, f"detector_train_{tag}.npz")
+        if os.path.exists(out):     # keys a committed file already has keep their values (the loss values above all)
+            old = np.load(out)
+            for k in PINNED:
+                assert old[k].dtype == data[k].dtype and np.array_equal(old[k], data[k]), (tag, k)
+        np.savez_compressed(out, **data)
+        print(out, os.path.getsize(out), "bytes")
+        assert os.path.getsize(out) < 1_000_000
+        for k in sorted(losses):
+            print(f"  {k:20s} {losses[k].item():.6f}")
 
 
 if __name__ == "__main__":

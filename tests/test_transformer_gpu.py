@@ -290,12 +290,23 @@ def test_config5_step_is_a_graph_of_at_most_240_launches():
         assert torch.equal(a, b)
 
 
+OWN_SCALE_FLOOR = 5e-6   # see test_whole_transformer_training_step_matches_reference_gradients
+
+
 @pytest.mark.parametrize("tag", ["plain", "neck"])
 def test_whole_transformer_training_step_matches_reference_gradients(gold, tag):
     """``SalienceTransformer.forward`` under autograd with denoising queries (salience_transformer.py:195-233; train mode:
     the neck's norms take batch statistics): the five outputs, the loss of fixed random weights on them and the gradients
     of a spread of parameters -- filtering head, encoder layers, proposal heads, neck, decoder, embeddings -- and of the
-    finest input level against what the imported reference produced (tests/golden/make_golden.py transformer_train)."""
+    finest input level against what the imported reference produced (tests/golden/make_golden.py transformer_train).
+
+    Two measures per gradient: ``max|g - ref| / max(1, max|ref|) < 2e-3``, which is absolute for small tensors (the
+    stored gradient of ``alpha`` has max|ref| = 5.2e-5: zero passes it), and on the tensor's own scale ``max|g - ref| /
+    max|ref| < max(4 * d_ref, OWN_SCALE_FLOOR)``, where ``d_ref`` is the distance of the reference's own fp32 step from
+    the same step in float64 (transformer_train_small_dref.npz, make_golden.py transformer_train_dref) and the floor is
+    the one tests/test_detector_train_gpu.py derives.  Measured on MI355X: worst 1.9 d_ref (neck,
+    ``encoder_bbox_head.layers.2.bias``: 1.8e-7 against 9.6e-8); ``alpha`` 9.7e-3 against d_ref 7.8e-3 in both fixtures;
+    the neck's tensors 1e-5 .. 2.4e-5 against d_ref 1e-5 .. 3.3e-5; no tensor needed the floor."""
     t = np.load(os.path.join(G, "transformer_train_small.npz"))
     neck_fixture = {"sd_keys": t["neck.sd_keys"], "sd_crc": t["neck.sd_crc"]} if tag == "neck" else None
     tr, sd = build_product_transformer(gold, neck_fixture)
@@ -318,7 +329,7 @@ def test_whole_transformer_training_step_matches_reference_gradients(gold, tag):
     assert abs(loss.item() - want_loss) < 2e-3 * max(1.0, abs(want_loss)), (loss.item(), want_loss)
     params = dict(tr.named_parameters(remove_duplicate=False))
     names = t["grad_names"].tolist() + (t["neck_grad_names"].tolist() if tag == "neck" else [])
-    worst = {}
+    worst, own = {}, {}
     for n in names:
         g = params[n].grad
         assert g is not None, n
@@ -328,10 +339,20 @@ def test_whole_transformer_training_step_matches_reference_gradients(gold, tag):
         ref = _t(t[f"{tag}.grad.{n}"])
         assert g.shape == ref.shape, n
         worst[n] = ((g - ref).abs().max() / max(1.0, ref.abs().max().item())).item()
+        own[n] = ((g - ref).abs().max() / ref.abs().max()).item(), ref.abs().max().item()
     gf = feats[0].grad.cpu()[:, ::8]
     ref = _t(t[f"{tag}.grad.feat0"])
     worst["feat0"] = ((gf - ref).abs().max() / max(1.0, ref.abs().max().item())).item()
+    own["feat0"] = ((gf - ref).abs().max() / ref.abs().max()).item(), ref.abs().max().item()
     bad = {n: e for n, e in worst.items() if not e < 2e-3}
+    assert not bad, bad
+    # on the tensor's own scale, against the reference's own fp32 rounding distance (docstring)
+    dref = np.load(os.path.join(G, "transformer_train_small_dref.npz"))
+    d_ref = dict(zip(dref[f"{tag}.names"].tolist(), dref[f"{tag}.d_ref"].tolist()))
+    assert set(d_ref) == set(own)
+    for n, (e, scale) in own.items():
+        print(f"{tag} {n:66s} max|ref| {scale:.3e} own-scale {e:.2e} d_ref {d_ref[n]:.2e} bar {max(4 * d_ref[n], OWN_SCALE_FLOOR):.2e}")
+    bad = {n: (e, d_ref[n]) for n, (e, scale) in own.items() if not e < max(4 * d_ref[n], OWN_SCALE_FLOOR)}
     assert not bad, bad
     if tag == "neck":   # the training-mode forward also moved the norms' running statistics, as nn.BatchNorm2d does
         bn = tr.neck.lateral_convs[0][1]
