@@ -1228,6 +1228,20 @@ int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, i
  * u8 [batch, canvas_height, canvas_width] = 1 on padding.  At most 64 images.  sdetr_backbone_batch_images_ex: the same
  * launch with a `normalize` switch; 0 copies the values as they are (training: images arrive normalised), so the canvas
  * equals the inputs bit for bit inside every image.
+ *
+ * EvalResize (models/detectors/base_detector.py:20-53 and :70, transforms/_functional_tensor.py:439-474), csrc/eval_resize.hip:
+ * the antialiased bilinear resize F.interpolate(img[None], size=(nh, nw), mode="bilinear", align_corners=False,
+ * antialias=True) -- per axis scale = in / out in fp32, support = max(scale, 1), triangle weights over the taps within
+ * `support` of scale * (i + 0.5), renormalised to sum 1; rows are summed along the width first.  out_hw host int
+ * [batch][2] = the size (nh_i, nw_i) image i is resized to, computed by the caller (the size rule is host arithmetic).
+ * Any shrink or stretch factor; every side at most 2^24; at most 64 images.  ONE launch each:
+ * sdetr_backbone_resize_images: outputs = host array of `batch` device pointers to [3, nh_i, nw_i] of the images' own
+ * type; u8 values are summed as 0..255 floats, rounded half to even and stored as u8 (what the reference's cast round
+ * trip does).  An image with (nh, nw) == (h, w) is copied bit for bit.
+ * sdetr_backbone_resize_batch_images: that same value (for u8: after that rounding, / 255) normalised, padded and masked
+ * as sdetr_backbone_batch_images does, with canvas and mask as described there and every element of both written by the
+ * launch; the resized sizes must fit the canvas.  Equal, bit for bit, to sdetr_backbone_batch_images on the outputs of
+ * sdetr_backbone_resize_images.
  * --------------------------------------------------------------------------------------------- */
 typedef struct sdetr_backbone_op {
     int op;
@@ -1267,6 +1281,11 @@ int sdetr_backbone_batch_images(sdetr_stream_t stream, const void *const *images
 int sdetr_backbone_batch_images_ex(sdetr_stream_t stream, const void *const *images, const int *image_hw, int batch,
                                    int is_uint8, int normalize, int canvas_height, int canvas_width, float *canvas,
                                    uint8_t *mask);
+int sdetr_backbone_resize_images(sdetr_stream_t stream, const void *const *images, const int *image_hw, const int *out_hw,
+                                 int batch, int is_uint8, void *const *outputs);
+int sdetr_backbone_resize_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw,
+                                       const int *out_hw, int batch, int is_uint8, int canvas_height, int canvas_width,
+                                       float *canvas, uint8_t *mask);
 
 /* ---------------------------------------------------------------------------------------------
  * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.

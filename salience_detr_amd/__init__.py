@@ -1,7 +1,8 @@
 """Salience-DETR on MI355X.  Modules are imported by name (``salience_detr_amd.detector`` ...); the training-side entry
 points are also reachable from the package, resolved on first use so that importing the package stays free of torch."""
 
-_LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "SalienceDETRHead": "detector"}
+_LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "SalienceDETRHead": "detector",
+         "EvalResize": "eval_resize", "eval_resize_size": "eval_resize", "batch_images": "backbone"}
 
 
 def __getattr__(name):

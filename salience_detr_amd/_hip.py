@@ -243,6 +243,8 @@ SIGNATURES = {
     "sdetr_backbone_run": (_i, [_p, _p, _i, _i, _p, _i64]),
     "sdetr_backbone_batch_images": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "sdetr_backbone_batch_images_ex": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "sdetr_backbone_resize_images": (_i, [_p, _p, _p, _p, _i, _i, _p]),
+    "sdetr_backbone_resize_batch_images": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "sdetr_cdn_queries": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                _p, _p, _p, _p]),
     "sdetr_cdn_label_grad": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),

@@ -422,15 +422,25 @@ class ResNetBackbone(nn.Module):
         return outputs
 
 
-def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: bool = True) -> Tuple[Tensor, Tensor]:
+def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: bool = True,
+                 resize: Optional[Tuple[int, Optional[int]]] = None) -> Tuple[Tensor, Tensor]:
     """ONE launch: ``images`` ``[3, h_i, w_i]`` (float in [0, 1], or uint8 read as ``v / 255``) normalised with the
     ImageNet mean / std and padded with 0 after normalisation into ``canvas`` ``[B, 3, Hp, Wp]`` (Hp, Wp = the largest
     size rounded up to ``size_divisible``) and ``mask`` ``[B, Hp, Wp]`` (bool, True on padding): the reference's eval
     ``ConvertImageDtype`` + ``Normalize`` + ``image_list_from_tensors`` + ``construct_mask``.  ``normalize=False`` (the
     reference's training mode, whose images arrive normalised from the dataset transforms: float32 only) only pads and
-    builds the mask: the canvas equals the inputs bit for bit inside every image."""
+    builds the mask: the canvas equals the inputs bit for bit inside every image.
+
+    ``resize=(min_size, max_size)`` puts the reference's ``EvalResize`` in front (``eval_resize.py``), still as ONE
+    launch: every image is resized to ``eval_resize_size(h, w, min_size, max_size)`` with the antialiased bilinear filter
+    (uint8: rounded to uint8 values first, as the reference's cast round trip), the canvas is sized from the RESIZED
+    sizes, and no resized image exists in memory.  Bit for bit ``batch_images([EvalResize(*resize)(i) for i in images])``.
+    Eval only: ``resize`` with ``normalize=False`` raises (the reference never resizes in training mode)."""
     if len(images) == 0:
         raise ValueError("batch_images: no images")
+    if resize is not None and not normalize:
+        raise ValueError("batch_images: resize is the eval transform's first step; it does not combine with "
+                         "normalize=False (the reference never resizes in training mode)")
     dev, dt = images[0].device, images[0].dtype
     if dt not in (torch.float32, torch.uint8):
         raise RuntimeError(f"batch_images: images must be float32 or uint8, got {dt}")
@@ -440,6 +450,8 @@ def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: 
         if im.dim() != 3 or im.shape[0] != 3 or im.dtype != dt or im.device != dev:
             raise RuntimeError("batch_images: every image must be [3, h, w] of one dtype on one device")
         _hip.require_device("batch_images", image=im)
+    if resize is not None:
+        return _resize_batch_images(images, size_divisible, resize)
     hp = -(-max(int(im.shape[1]) for im in images) // size_divisible) * size_divisible
     wp = -(-max(int(im.shape[2]) for im in images) // size_divisible) * size_divisible
     canvas = torch.empty(len(images), 3, hp, wp, device=dev, dtype=torch.float32)
@@ -450,4 +462,28 @@ def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: 
     _hip.check(lib.sdetr_backbone_batch_images_ex(_hip.stream_ptr(), ptrs, hw, len(images), 1 if dt == torch.uint8 else 0,
                                                   1 if normalize else 0, hp, wp, canvas.data_ptr(), mask.data_ptr()),
                "batch_images", lib)
+    return canvas, mask
+
+
+def _resize_batch_images(images: Sequence[Tensor], size_divisible: int, resize) -> Tuple[Tensor, Tensor]:
+    """The fused form of ``batch_images`` (``sdetr_backbone_resize_batch_images``); ``images`` already checked."""
+    from .eval_resize import MAX_IMAGES, eval_resize_size
+    min_size, max_size = resize
+    if len(images) > MAX_IMAGES:
+        raise ValueError(f"batch_images: at most {MAX_IMAGES} images per call, got {len(images)}")
+    dev, dt = images[0].device, images[0].dtype
+    sizes = [eval_resize_size(im.shape[1], im.shape[2], min_size, max_size) for im in images]
+    if any(nh < 1 or nw < 1 for nh, nw in sizes):
+        raise ValueError(f"batch_images: resize={tuple(resize)} leaves an image without pixels (sizes {sizes})")
+    hp = -(-max(nh for nh, _ in sizes) // size_divisible) * size_divisible
+    wp = -(-max(nw for _, nw in sizes) // size_divisible) * size_divisible
+    canvas = torch.empty(len(images), 3, hp, wp, device=dev, dtype=torch.float32)
+    mask = torch.empty(len(images), hp, wp, device=dev, dtype=torch.bool)
+    ptrs = (ctypes.c_void_p * len(images))(*[im.data_ptr() for im in images])
+    hw = (ctypes.c_int * (2 * len(images)))(*[int(v) for im in images for v in im.shape[1:]])
+    out_hw = (ctypes.c_int * (2 * len(images)))(*[v for s in sizes for v in s])
+    lib = _hip.lib()
+    _hip.check(lib.sdetr_backbone_resize_batch_images(_hip.stream_ptr(), ptrs, hw, out_hw, len(images),
+                                                      1 if dt == torch.uint8 else 0, hp, wp, canvas.data_ptr(),
+                                                      mask.data_ptr()), "batch_images (resize)", lib)
     return canvas, mask

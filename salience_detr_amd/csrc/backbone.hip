@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "image_norm.h"
 
 namespace sdetr {
 namespace {
@@ -429,7 +430,6 @@ struct BatchArgs {
 // `normalize` the value itself (bit for bit)
 __global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
 {
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
     const int64_t plane = (int64_t)a.hp * a.wp, total = a.batch * plane, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
         const int b = (int)(e / plane);
@@ -441,9 +441,9 @@ __global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
             float v = 0.f;
             if (in) {
                 const int64_t src = ((int64_t)ch * h + y) * w + x;
-                const float raw = a.is_u8 ? (float)reinterpret_cast<const uint8_t *>(a.img[b])[src] / 255.f
+                const float raw = a.is_u8 ? image_unit_from_u8((float)reinterpret_cast<const uint8_t *>(a.img[b])[src])
                                           : reinterpret_cast<const float *>(a.img[b])[src];
-                v = a.normalize ? (raw - mean[ch]) / sd[ch] : raw;
+                v = a.normalize ? image_normalize(raw, ch) : raw;
             }
             a.canvas[((int64_t)b * 3 + ch) * plane + p] = v;
         }

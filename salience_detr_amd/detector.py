@@ -12,8 +12,15 @@ reference ``SalienceDETR`` state dict loads once its ``denoising_generator.*`` a
 (``detector_state_dict``).  ``forward(images)`` runs image batching (one launch: ``ConvertImageDtype`` + ``Normalize`` +
 padding to a multiple of 32 + the padding mask) -> backbone -> the head above, handing the transformer the image sizes
 and the canvas so that its token budgets come from the host.  (The transformer's proposal stage still reads its kept
-count on the host, so the whole detector does not capture into one graph; batching + backbone do.)  Out of scope: ``EvalResize`` (images
-arrive already at model size, the training path's contract).
+count on the host, so the whole detector does not capture into one graph; batching + backbone do.)
+
+``SalienceDETR(..., min_size=, max_size=)`` (the reference constructor's keywords and rule, base_detector.py:57-75: the
+transform exists when at least one is a number, with ``min(size)``, ``max(size)``) puts the reference's ``EvalResize`` in
+front of the eval path, fused into the batching launch (``batch_images(images, resize=...)``): the canvas and the
+transformer's token budgets come from the RESIZED sizes, ``PostProcess`` gets the sizes BEFORE the resize, so the boxes
+are in the original image's pixels (salience_detr.py:165).  Training mode ignores it, as the reference does (its
+training images are resized by the dataset transforms).  ``EvalResize`` has no parameters or buffers: state dicts are
+the same with and without it, and a detector built without the keywords has today's module tree and path.
 
 Training (``criterion=`` given, ``train()`` mode, ``forward(images, targets)``; salience_detr.py:163-240,
 base_detector.py:156-261): images are batched WITHOUT the eval transform (they arrive normalised from the dataset
@@ -225,12 +232,18 @@ class SalienceDETR(SalienceDETRHead):
     def __init__(self, backbone: nn.Module, neck: nn.Module, position_embedding: nn.Module, transformer: nn.Module,
                  postprocessor: nn.Module, criterion: Optional[nn.Module] = None,
                  focus_criterion: Optional[nn.Module] = None, num_classes: int = 91, num_queries: int = 900,
-                 denoising_nums: int = 100, aux_loss: bool = True):
+                 denoising_nums: int = 100, aux_loss: bool = True, min_size: Optional[int] = None,
+                 max_size: Optional[int] = None):
         super().__init__(neck, position_embedding, transformer, postprocessor, criterion=criterion,
                          focus_criterion=focus_criterion, num_classes=num_classes, num_queries=num_queries,
                          denoising_nums=denoising_nums, aux_loss=aux_loss)
         self.backbone = backbone
         self._sizes_cache = {}
+        # base_detector.py:68-72: the resize exists when at least one of the two is a number
+        size = [s for s in (min_size, max_size) if isinstance(s, (int, float)) and not isinstance(s, bool)]
+        if len(size) != 0:
+            from .eval_resize import EvalResize
+            self.eval_resize = EvalResize(min(size), max(size), antialias=True)
 
     def set_dtype(self, dtype: torch.dtype):
         if hasattr(self.backbone, "set_dtype"):
@@ -238,7 +251,9 @@ class SalienceDETR(SalienceDETRHead):
         return super().set_dtype(dtype)
 
     def forward(self, images: Sequence[Tensor], targets: Optional[Sequence[Dict[str, Tensor]]] = None, noise=None):
-        """``images``: ``[3, h_i, w_i]`` each, already at model size (no ``EvalResize``).  Eval mode (or a detector built
+        """``images``: ``[3, h_i, w_i]`` each; in eval mode of any size when the detector was built with ``min_size`` /
+        ``max_size`` (they are resized in the batching launch and the boxes come back in the original pixels), otherwise
+        already at model size.  Eval mode (or a detector built
         without ``criterion``): float in [0, 1] or uint8, returns the detections under ``no_grad``.  Training mode:
         float32, already normalised by the dataset transforms; ``targets[i]`` = ``{"boxes": [n, 4] xyxy pixels of image
         i, "labels": [n]}``, required (``None`` raises); returns the weighted loss dict.  A detector built without
@@ -261,7 +276,12 @@ class SalienceDETR(SalienceDETRHead):
         if self._sizes_cache.get("key") != key:   # one host-to-device copy per distinct batch of sizes
             self._sizes_cache = {"key": key, "value": torch.tensor(sizes, device=images[0].device)}
         original_image_sizes = self._sizes_cache["value"]
-        canvas, mask = batch_images(images)
+        resize = getattr(self, "eval_resize", None)
+        if resize is None:
+            canvas, mask = batch_images(images)
+        else:   # boxes in the ORIGINAL pixels (sizes before the resize), token budgets from the RESIZED sizes
+            canvas, mask = batch_images(images, resize=(resize.min_size, resize.max_size))
+            sizes = tuple(resize.output_size(h, w) for h, w in sizes)
         # the image sizes and the canvas give the transformer its token budgets on the host (one device sync fewer)
         return self._detect(self.backbone(canvas), mask, original_image_sizes, image_sizes=[list(s) for s in sizes],
                             canvas=tuple(canvas.shape[-2:]))
