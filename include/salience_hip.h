@@ -1316,6 +1316,64 @@ int sdetr_cdn_queries(sdetr_stream_t stream, const float *boxes, const int *labe
 int sdetr_cdn_label_grad(sdetr_stream_t stream, const float *grad_label_queries, const int *noised_labels, int batch,
                          int n_dn, int num_classes, int embed_dim, float *grad_weight);
 
+/* ---------------------------------------------------------------------------------------------
+ * The optimizer step (reference util/engine.py:56-61: clip_grad_norm_(parameters, max_norm) + torch.optim.AdamW.step()),
+ * csrc/optimizer.hip: TWO launches over every parameter that has a gradient.  All arithmetic fp32 (the norm's sum and the
+ * per-step scalars in double), bit-identical from run to run and under hipGraph replay: no atomics, no memset, nothing
+ * copied from the host inside the two calls.
+ *
+ * Device tables (the caller builds them; the kernels skip an entry that does not fit the tables, they never follow it):
+ *   records    one per tensor: param / grad fp32 pointers of `length` elements, `moment_offset` = first element of the
+ *              tensor in the flat exp_avg / exp_avg_sq buffers (choose it congruent to (param address / 4) mod 4 so that
+ *              the moments are 16-byte aligned where the parameter is), `group` = row of group_table, `lag` = steps of the
+ *              shared counter this tensor did not take (its bias corrections use counter - lag; 0 <= lag < counter).
+ *   chunks     (record, start, count): count in [1, SDETR_ADAMW_CHUNK] elements of one tensor, start a multiple of
+ *              SDETR_ADAMW_CHUNK.
+ *   wave_first [num_waves + 1], non-decreasing, wave_first[0] = 0, wave_first[num_waves] = num_chunks: wave item w updates
+ *              chunks wave_first[w] .. wave_first[w + 1] - 1 (pack small tensors: together at most SDETR_ADAMW_CHUNK
+ *              elements per item).  Every element of every tensor belongs to exactly one chunk.
+ *
+ * sdetr_adamw_grad_sumsq: launch 1.  partials f64 [num_partials], num_partials in [1, min(SDETR_ADAMW_MAX_PARTIALS,
+ * num_waves)]: partials[b] = sum of grad^2 over wave items [b * per, (b + 1) * per), per = ceil(num_waves / num_partials),
+ * in a fixed order; every partial is written.  Adds 1 to *step_counter (int32, device).
+ *
+ * sdetr_adamw_clip_step: launch 2 (same tables and num_partials).  total_norm = float(grad_scale * sqrt(sum of partials))
+ * is written to *total_norm; coef = min(1, max_norm / (total_norm + 1e-6)) (max_norm <= 0: 1; a NaN stays a NaN);
+ * g' = g * (grad_scale * coef); with t = *step_counter - lag and (lr, wd) = group_table[group] (f64 [num_groups, 2]):
+ *   p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);  v = v * beta2 + (1 - beta2) * g' * g';
+ *   p += (-lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * (torch.optim.AdamW, amsgrad=False, maximize=False).  Writes param, exp_avg, exp_avg_sq; never grad.
+ * --------------------------------------------------------------------------------------------- */
+#define SDETR_ADAMW_CHUNK 1024
+#define SDETR_ADAMW_MAX_PARTIALS 1024
+
+typedef struct sdetr_adamw_record {
+    float *param;
+    const float *grad;
+    int64_t moment_offset;
+    int64_t length;
+    int group;
+    int lag;
+} sdetr_adamw_record;
+
+typedef struct sdetr_adamw_chunk {
+    int record;
+    int start;
+    int count;
+    int reserved;
+} sdetr_adamw_chunk;
+
+int sdetr_adamw_chunk_elements(void);
+int sdetr_adamw_max_partials(void);
+int sdetr_adamw_grad_sumsq(sdetr_stream_t stream, const sdetr_adamw_record *records, int num_records,
+                           const sdetr_adamw_chunk *chunks, int num_chunks, const int *wave_first, int num_waves,
+                           int num_partials, double *partials, int *step_counter);
+int sdetr_adamw_clip_step(sdetr_stream_t stream, const sdetr_adamw_record *records, int num_records,
+                          const sdetr_adamw_chunk *chunks, int num_chunks, const int *wave_first, int num_waves,
+                          int num_partials, const double *partials, const int *step_counter, const double *group_table,
+                          int num_groups, float *exp_avg, float *exp_avg_sq, double beta1, double beta2, double eps,
+                          float max_norm, float grad_scale, float *total_norm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,11 @@ SIGNATURES = {
     "sdetr_cdn_queries": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                _p, _p, _p, _p]),
     "sdetr_cdn_label_grad": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "sdetr_adamw_chunk_elements": (_i, []),
+    "sdetr_adamw_max_partials": (_i, []),
+    "sdetr_adamw_grad_sumsq": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _p, _p]),
+    "sdetr_adamw_clip_step": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _i, _p, _p] + [ctypes.c_double] * 3
+                              + [ctypes.c_float] * 2 + [_p]),
 }
 
 

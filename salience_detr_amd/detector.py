@@ -135,11 +135,14 @@ class SalienceDETRHead(nn.Module):
     def forward_train(self, backbone_feats: Union[Dict[str, Tensor], Sequence[Tensor]], mask: Tensor,
                       targets: Sequence[Dict[str, Tensor]], image_sizes: Sequence[Sequence[int]],
                       canvas: Optional[Tuple[int, int]] = None, noise: Optional[Tensor] = None,
-                      staged: Optional[StagedTargets] = None) -> Dict[str, Tensor]:
+                      staged: Optional[StagedTargets] = None,
+                      focus_boxes: Optional[Tuple[Tensor, Tensor]] = None) -> Dict[str, Tensor]:
         """The training half of the reference's forward (salience_detr.py:170-240) from backbone features.  ``targets``:
         prepared (``prepare_targets``: cxcywh in [0, 1]); ``image_sizes``: (h, w) of every image before padding;
         ``canvas``: the padded (H, W), default ``mask.shape[-2:]``; ``noise``: the generator's noise tensor (tests);
-        ``staged``: the batch's ``stage_targets(...)`` when the caller already has it."""
+        ``staged``: the batch's ``stage_targets(...)`` when the caller already has it; ``focus_boxes``: the salience
+        criterion's ``stage_boxes(targets, image_sizes, device)`` likewise (with both, the call makes no host-to-device
+        copy: a captured step)."""
         if self.criterion is None:
             raise RuntimeError(f"{type(self).__name__}: built without a criterion; there is no training forward")
         if len(targets) != mask.shape[0] or len(image_sizes) != mask.shape[0]:
@@ -173,7 +176,7 @@ class SalienceDETRHead(nn.Module):
                 loss_dict.update({k + suffix: zero for k in ("loss_class", "loss_bbox", "loss_giou")})
         if self.focus_criterion is not None:
             feature_stride = [(canvas[0] / f.shape[-2], canvas[1] / f.shape[-1]) for f in feats]
-            boxes = self.focus_criterion.stage_boxes(
+            boxes = focus_boxes if focus_boxes is not None else self.focus_criterion.stage_boxes(
                 [{"boxes": staged.boxes[o:o + n]} for o, n in self._staged_slices(staged, targets)],
                 image_sizes, dev)
             loss_dict.update(self.focus_criterion(foreground_mask, targets, feature_stride, image_sizes, staged=boxes))
