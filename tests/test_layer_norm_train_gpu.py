@@ -3,6 +3,8 @@ torch's own fp32 LayerNorm meets on the same operands."""
 import pytest
 import torch
 
+import layer_norm_cases as LC
+
 from salience_detr_amd import layer_norm_train as L
 from salience_detr_amd import synthetic as syn
 
@@ -17,33 +19,13 @@ def _err(got, want64):
 @pytest.mark.parametrize("shape", [(1, 1, 256), (2, 300, 256), (2, 11363, 256), (3, 1001, 64), (5, 77, 128), (2, 130, 512)])
 @pytest.mark.parametrize("with_residual", [True, False])
 def test_add_layer_norm_forward_backward_match_float64(shape, with_residual):
-    C = shape[-1]
-    x = syn.det_randn(f"ln.x{shape}", shape) * 2 + 0.5
-    r = syn.det_randn(f"ln.r{shape}", shape) if with_residual else None
-    gy = syn.det_randn(f"ln.g{shape}", shape)
-    norm = torch.nn.LayerNorm(C)
-    with torch.no_grad():
-        norm.weight.copy_(syn.det_randn(f"ln.w{C}", (C,)) * 0.3 + 1)
-        norm.bias.copy_(syn.det_randn(f"ln.b{C}", (C,)))
-
-    def run(dtype, device, fused):
-        n = torch.nn.LayerNorm(C).to(device=device, dtype=dtype)
-        n.load_state_dict({k: v.to(dtype) for k, v in norm.state_dict().items()})
-        xx = x.to(device=device, dtype=dtype).requires_grad_(True)
-        rr = None if r is None else r.to(device=device, dtype=dtype).requires_grad_(True)
-        y = L.add_layer_norm(xx, n, rr) if fused else n(xx if rr is None else xx + rr)
-        y.backward(gy.to(device=device, dtype=dtype))
-        return y.detach(), xx.grad, None if rr is None else rr.grad, n.weight.grad, n.bias.grad
-
-    want = run(torch.float64, "cpu", False)
-    ref = run(torch.float32, DEV, False)
+    ops = LC.operands(shape, with_residual)
+    x, r, _, norm = ops
+    want = LC.run(ops, torch.float64, "cpu", False)
+    ref = LC.run(ops, torch.float32, DEV, False)
     assert L.applies(x.to(DEV), norm.to(DEV), None if r is None else r.to(DEV))
-    got = run(torch.float32, DEV, True)
-    for g, f, w in zip(got, ref, want):
-        if w is None:
-            assert g is None
-            continue
-        assert _err(g, w) <= max(3.0 * _err(f, w), 2e-6)
+    got = LC.run(ops, torch.float32, DEV, True)
+    LC.assert_within_bar(got, ref, want)
 
 
 def test_add_layer_norm_falls_back_where_the_kernel_does_not_apply():

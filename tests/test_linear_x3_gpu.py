@@ -3,6 +3,8 @@ error bar is the one torch's own fp32 matmul meets on the same operands."""
 import pytest
 import torch
 
+import linear_x3_cases as LC
+
 from salience_detr_amd import linear_x3 as X
 from salience_detr_amd import synthetic as syn
 
@@ -91,33 +93,13 @@ def test_gemm_x3_bias_and_argument_checks(generation):
         X.gemm_x3(a[:, :62].contiguous(), True, b[:, :62].contiguous(), True, 70, 36, 62)
 
 
-@pytest.mark.parametrize("shape,N", [((2, 1137, 256), 2048), ((3000, 2048), 256), ((2, 300, 256), 384)])
+@pytest.mark.parametrize("shape,N", LC.LINEAR_SHAPES)
 def test_x3_linear_forward_backward_match_float64(shape, N, monkeypatch, generation):
-    for flag in ("X3_FORWARD", "X3_DX", "X3_DW"):   # all three products through the kernel under test
-        monkeypatch.setattr(X, flag, True)
-    monkeypatch.setattr(X, "X3_WIDE_OUT_ROWS", 1)
-    monkeypatch.setattr(X, "X3_WIDE_FEATURES", 1)
-    K = shape[-1]
-    lin = torch.nn.Linear(K, N)
-    x = syn.det_randn(f"lx{N}", shape)
-    gy = syn.det_randn(f"lg{N}", shape[:-1] + (N,))
-    x64 = x.double().requires_grad_(True)
-    l64 = torch.nn.Linear(K, N).double()
-    l64.load_state_dict({k: v.double() for k, v in lin.state_dict().items()})
-    l64(x64).backward(gy.double())
-    xd = x.to(DEV).requires_grad_(True)
-    ld = torch.nn.Linear(K, N).to(DEV)
-    ld.load_state_dict(lin.state_dict())
-    assert X.use_x3_linear_(ld) == 1 and isinstance(ld, X.X3Linear)
-    y = ld(xd)
-    y.backward(gy.to(DEV))
-    xr = x.to(DEV).requires_grad_(True)
-    lr = torch.nn.Linear(K, N).to(DEV)
-    lr.load_state_dict(lin.state_dict())
-    lr(xr).backward(gy.to(DEV))
-    for got, ref, want in ((y, lr(xr), l64(x64)), (xd.grad, xr.grad, x64.grad), (ld.weight.grad, lr.weight.grad, l64.weight.grad),
-                           (ld.bias.grad, lr.bias.grad, l64.bias.grad)):
-        assert _err(got.detach(), want.detach()) <= max(3.0 * _err(ref.detach(), want.detach()), 3e-6)
+    LC.force_every_product_through_x3(monkeypatch)
+    want = LC.linear_float64(shape, N)
+    got = LC.linear_device_run(shape, N, x3=True)
+    ref = LC.linear_device_run(shape, N, x3=False)
+    LC.assert_within_bar(got, ref, want)
 
 
 def test_x3_linear_falls_back_where_the_kernel_does_not_apply():
@@ -153,40 +135,12 @@ def test_gemm_x3_relu_and_gate_epilogues(M, N, K, generation):
         X.gemm_x3(a, True, b, True, M, N, K, epilogue=X.EPI_GATE)
 
 
-@pytest.mark.parametrize("rows,wide", [((2, 1137), True), ((2, 1137), False), ((2, 11363), None)])
+@pytest.mark.parametrize("rows,wide", LC.FFN_CASES)
 def test_x3_ffn_matches_the_unfused_modules(rows, wide, monkeypatch):
     """linear2(relu(linear1(x))) as one autograd node (ReLU in the products' epilogues) against the same layers as
     separate X3Linear modules + nn.ReLU, and both against float64.  wide = True / False forces every product through
     the x3 kernel / the library's GEMM; None = the shipped shape routing at the benchmark's layer-0 size."""
-    if wide is not None:
-        monkeypatch.setattr(X, "X3_WIDE_OUT_ROWS", 1 if wide else 10 ** 9)
-        monkeypatch.setattr(X, "X3_LONG_REDUCTION_ROWS", 1 if wide else 10 ** 9)
-    l1, l2 = torch.nn.Linear(256, 2048), torch.nn.Linear(2048, 256)
-    x = syn.det_randn("ffn_x", rows + (256,))
-    gy = syn.det_randn("ffn_gy", rows + (256,))
-    x64 = x.double().requires_grad_(True)
-    a64, b64 = torch.nn.Linear(256, 2048).double(), torch.nn.Linear(2048, 256).double()
-    a64.load_state_dict({k: v.double() for k, v in l1.state_dict().items()})
-    b64.load_state_dict({k: v.double() for k, v in l2.state_dict().items()})
-    y64 = b64(torch.relu(a64(x64)))
-    y64.backward(gy.double())
-
-    def run(fused):
-        m1, m2 = torch.nn.Linear(256, 2048).to(DEV), torch.nn.Linear(2048, 256).to(DEV)
-        m1.load_state_dict(l1.state_dict())
-        m2.load_state_dict(l2.state_dict())
-        seq = torch.nn.Sequential(m1, m2)
-        assert X.use_x3_linear_(seq) == 2
-        xd = x.to(DEV).requires_grad_(True)
-        if fused:
-            assert X.x3_ffn_applies(xd, m1, m2)
-            y = X.x3_ffn(xd, m1, m2)
-        else:
-            y = m2(torch.relu(m1(xd)))
-        y.backward(gy.to(DEV))
-        return y.detach(), xd.grad, m1.weight.grad, m1.bias.grad, m2.weight.grad, m2.bias.grad
-
-    fused, plain = run(True), run(False)
-    want = (y64.detach(), x64.grad, a64.weight.grad, a64.bias.grad, b64.weight.grad, b64.bias.grad)
-    for got, ref, w in zip(fused, plain, want):
-        assert _err(got, w) <= max(3.0 * _err(ref, w), 3e-6)
+    LC.route_ffn(monkeypatch, wide)
+    want = LC.ffn_float64(rows)
+    fused, plain = LC.ffn_device_run(rows, True), LC.ffn_device_run(rows, False)
+    LC.assert_within_bar(fused, plain, want)

@@ -5,52 +5,31 @@ import numpy as np
 import pytest
 import torch
 
+import msda_cases as MC
+
 from oracle import msda_c
 from salience_detr_amd import ms_deform_attn as M
 from salience_detr_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-LEVELS_SMALL = [(20, 30), (10, 15), (5, 8), (3, 4)]
-LEVELS_FULL = [(100, 168), (50, 84), (25, 42), (13, 21)]
-LEVELS_TILED = [(40, 70), (33, 40), (5, 8)]     # two tiled levels (2800 and 1320 pixels) and one held whole
-
-
-def _smooth_mask(loc, shapes):
-    # d(out)/d(loc) jumps where a sample sits on a pixel boundary; 1 ulp in loc*size-0.5 flips floor() there
-    px = loc * torch.stack([shapes[:, 1], shapes[:, 0]], -1).float()[None, None, None, :, None, :] - 0.5
-    return ((px - px.round()).abs() > 1e-3).all(-1, keepdim=True).expand_as(loc).numpy()
+LEVELS_SMALL, LEVELS_FULL, LEVELS_TILED = MC.LEVELS_SMALL, MC.LEVELS_FULL, MC.LEVELS_TILED
+_smooth_mask = MC.smooth_mask
 
 
 def _run(lds, value, shapes, lsi, loc, aw, go):
-    old = M.lds_backward, M.lds_backward_min_queries
-    M.lds_backward, M.lds_backward_min_queries = lds, 1    # the kernel under test, whatever the query count
-    try:
+    with MC.forced_backward_kernel(lds):    # the kernel under test, whatever the query count
         out = M.ms_deform_attn_backward(value, shapes, lsi, loc, aw, go, 64)
         torch.cuda.synchronize()
         return [t.cpu().numpy() for t in out], M.last_backward_kernel()
-    finally:
-        M.lds_backward, M.lds_backward_min_queries = old
 
 
-@pytest.mark.parametrize("B,Nq,levels,M_,spread", [
-    (2, 333, LEVELS_SMALL, 8, 4.0),      # every level held whole
-    (1, 700, LEVELS_TILED, 3, 4.0),      # tiled levels, 3 heads
-    (2, 1500, LEVELS_TILED, 8, 12.0),    # offsets beyond the halo: per-sample fallback to global atomics
-    (2, 2272, LEVELS_FULL, 8, 6.0),      # encoder layer 5 at the benchmark shape
-])
+@pytest.mark.parametrize("B,Nq,levels,M_,spread", MC.LDS_CASES)
 def test_lds_backward_vs_c_oracle(B, Nq, levels, M_, spread):
-    value, shapes, lsi, loc, aw = syn.make_msda_inputs(B, Nq, levels, M_, 32, 4, seed=3, spread_px=spread)
-    go = syn.det_randn("gout_lds", (B, Nq, M_ * 32))
-    rgv, rgl, rga = msda_c.msda_backward(value.numpy(), shapes.numpy(), lsi.numpy(), loc.numpy(), aw.numpy(), go.numpy())
-    dev = [t.to(DEV) for t in (value, shapes, lsi, loc, aw, go)]
-    (gv, gl, ga), which = _run(True, *dev)
+    case = MC.oracle_case(B, Nq, levels, M_, 32, 4, seed=3, spread=spread, gout_name="gout_lds")
+    (gv, gl, ga), which = _run(True, *case.on(DEV))
     assert which == M.KERNEL_BWD_LDS
-    smooth = _smooth_mask(loc, shapes)
-    assert smooth.mean() > 0.99
-    assert np.abs(gv - rgv).max() < 2e-4 * max(1.0, np.abs(rgv).max())
-    assert np.abs((gl - rgl) * smooth).max() < 2e-4 * max(1.0, np.abs(rgl).max())
-    assert np.abs(ga - rga).max() < 2e-4 * max(1.0, np.abs(rga).max())
+    case.assert_within_bar(gv, gl, ga)
 
 
 @pytest.mark.parametrize("Nq", [257, 11363])

@@ -68,24 +68,8 @@ def test_full_size_training_step_matches_oracle_autograd():
         return loss.detach()
 
     # instrumentation for the comparison below: every layer's top-300 positions and the sorted index list they refer to
-    from salience_detr_amd import salience_encoder as SE
-    picked, lists = [], []
-    real_topk = SE.masked_topk_desc
-
-    def recording_topk(score, k, *a, **kw):
-        r = real_topk(score, k, *a, **kw)
-        if k == 300:
-            picked.append(r[1].detach().cpu())
-        return r
-
-    hook = m.encoder.register_forward_pre_hook(lambda mod, a, kw: lists.append(kw["foreground_inds"][0].detach().cpu()),
-                                               with_kwargs=True)
-    SE.masked_topk_desc = recording_topk
-    try:
+    with C.record_top300(m) as (picked, lists):
         loss = forward_backward()
-    finally:
-        SE.masked_topk_desc = real_topk
-        hook.remove()
     torch.cuda.synchronize()
     # top-300 sets of each layer, both sides as TOKEN ids (each side's positions through its own sorted list): a near-tie
     # of the class score may fall the other way (fp32 on both sides, different summation orders), and a layer with a flipped

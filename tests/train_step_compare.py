@@ -1,5 +1,7 @@
 """Shared by the full-size training-step tests (CPU: oracle autograd against the reference fixture; GPU: the HIP step
 against both): how a gradient is compared, and the fixture's sub-sampling (tests/golden/make_golden.py `sub`)."""
+import contextlib
+
 import torch
 
 
@@ -33,3 +35,28 @@ def compare(got: torch.Tensor, ref: torch.Tensor, name: str, scale: float = None
 def loss_fn(memory, score_maps, w, mean=lambda t: t.mean()):
     """`train_full_loss` of tests/golden/make_golden.py."""
     return mean(memory * w) * 100.0 + sum((s * s).mean() for s in score_maps)
+
+
+@contextlib.contextmanager
+def record_top300(m):
+    """While the block runs a step of the hot path ``m``: every encoder layer's top-300 positions (``picked``, one entry
+    per layer) and the sorted index list they refer to (``lists``, one entry per forward).  ``lists[0][0][picked[k][0]]``
+    are layer k's tokens of image 0."""
+    from salience_detr_amd import salience_encoder as SE
+    picked, lists = [], []
+    real_topk = SE.masked_topk_desc
+
+    def recording_topk(score, k, *a, **kw):
+        r = real_topk(score, k, *a, **kw)
+        if k == 300:
+            picked.append(r[1].detach().cpu())
+        return r
+
+    hook = m.encoder.register_forward_pre_hook(lambda mod, a, kw: lists.append(kw["foreground_inds"][0].detach().cpu()),
+                                               with_kwargs=True)
+    SE.masked_topk_desc = recording_topk
+    try:
+        yield picked, lists
+    finally:
+        SE.masked_topk_desc = real_topk
+        hook.remove()
