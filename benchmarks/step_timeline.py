@@ -10,9 +10,10 @@ import sys
 def main():
     rows = list(csv.DictReader(open(sys.argv[1])))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    # a step starts at its first flatten launch (one for the whole pyramid, or one per level back to back)
-    first = [i for i, r in enumerate(rows) if "pyramid_flatten" in r["Kernel_Name"]
-             and (i == 0 or "pyramid_flatten" not in rows[i - 1]["Kernel_Name"])]
+    # a step starts at its first flatten launch (one for the whole pyramid, or one per level back to back) -- or at the
+    # hoisted stage 1 that reads the pyramid itself (salience_head_hoist_pyramid_kernel)
+    opens = lambda name: "pyramid_flatten" in name or "hoist_pyramid" in name
+    first = [i for i, r in enumerate(rows) if opens(r["Kernel_Name"]) and (i == 0 or not opens(rows[i - 1]["Kernel_Name"]))]
     k = int(sys.argv[2]) if len(sys.argv) > 2 else len(first) // 2
     s, e = first[k], first[k + 1]
     t0 = int(rows[s]["Start_Timestamp"])

@@ -572,6 +572,21 @@ int sdetr_salience_head_hoist_x3(
     const void *vp_x, const void *vp_packed_weight, const float *vp_bias_padded, const uint8_t *vp_pad_mask,
     int vp_batch_size, int vp_spatial_size, int vp_num_heads, int vp_num_groups, void *vp_dst, int vp_dst_dtype,
     const sdetr_bordered_layout *vp_bordered, const sdetr_finalize_job *finalize);
+/* sdetr_pyramid_flatten and sdetr_salience_head_hoist_x3 in ONE launch, for the 16-bit encoder (nothing else read the fp32
+ * enc_output input the flatten wrote: 45.7 MB at 2 x 800 x 1333, written and read back once).  Every 32-token tile of the
+ * hoisted stage 1 reads the fp32 NCHW feature / position maps of its tokens itself, builds (feat + (pos + level_embed)) *
+ * keep with the flatten's arithmetic -- the same bits -- and writes what the flatten wrote for the rest of the step:
+ * feat_act / pos_act [B, S, C] (16-bit activations of the library's flavour; pos with the level embedding), mask_out [B, S],
+ * valid_ratios [B, num_levels, 2] (may be NULL).  Pyramid arguments as sdetr_pyramid_flatten (HOST arrays of device
+ * pointers / sizes; at most 4 levels may meet inside one 32-token tile), head arguments as sdetr_salience_head_hoist_x3
+ * with enc_output required; no jobs ride on this launch (they read feat_act). */
+int sdetr_salience_head_hoist_pyramid_x3(
+    sdetr_stream_t stream, int num_levels, const float *const *feats, const float *const *pos, const uint8_t *const *masks,
+    const int *heights, const int *widths, const float *level_embeds, int batch_size, int channels, int spatial_size,
+    uint8_t *mask_out, void *feat_act, void *pos_act, float *valid_ratios, const void *enc_weight_x3, const float *enc_bias,
+    const float *enc_norm_weight, const float *enc_norm_bias, float enc_norm_eps, const float *norm_weight,
+    const void *weight_x3, float *memory_out, int64_t memory_batch_stride, float *g_out, int64_t g_batch_stride,
+    float *sigma_out, int64_t sigma_batch_stride);
 int sdetr_salience_head_modulate(sdetr_stream_t stream, const float *g, int64_t g_batch_stride, const float *sigma,
                                  int64_t sigma_batch_stride, int batch_size, int tokens, const float *row_scale,
                                  const float *coarse_score, int coarse_h, int coarse_w, int level_h, int level_w,

@@ -177,6 +177,8 @@ SIGNATURES = {
                                              _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "sdetr_salience_head_hoist_x3": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _p, _p, _p, _p, ctypes.c_float, _p, _p, _p, _i64, _p,
                                           _i64, _p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p]),
+    "sdetr_salience_head_hoist_pyramid_x3": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                  ctypes.c_float, _p, _p, _p, _i64, _p, _i64, _p, _i64]),
     "sdetr_salience_head_modulate": (_i, [_p, _p, _i64, _p, _i64, _i, _i, _p, _p, _i, _i, _i, _i, _p, ctypes.c_float, _p, _p, _p,
                                           _p, _p, _p]),
     "sdetr_stage1_x3_with_jobs": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i, _i,

@@ -33,6 +33,13 @@ __global__ void __launch_bounds__(512, 2) salience_head_stage1_x3_kernel(Stage1A
     stage1_x3_body(p, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+// The hoisted stage 1 (all levels' tokens of an image as one row of tiles) straight from the fp32 NCHW pyramid: the PYR form
+// of stage1_x3_body (salience_head_core.h) -- the flatten's launch and its enc_in round trip folded into this one.
+__global__ void __launch_bounds__(512, 2) salience_head_hoist_pyramid_kernel(Stage1Args p, PyramidSrc src, int s1_blocks)
+{
+    const int blk = (int)blockIdx.x;
+    stage1_x3_body<true>(p, blk % s1_blocks, blk / s1_blocks, &src);
+}
 
 // WAVES = 8 (512 threads, one column tile per wave) halves a block's latency -- two chained 256 x 256 fp32 GEMMs of
 // 64-cycle MFMAs, ~7 us each with four waves -- for the coarse levels, whose few blocks leave the chip idle anyway.
@@ -428,6 +435,71 @@ extern "C" int sdetr_salience_head_stage1_x3(sdetr_stream_t stream, const float 
     hipLaunchKernelGGL(salience_head_stage1_x3_kernel, dim3((unsigned)a.nblk, (unsigned)batch_size), dim3(512),
                        (size_t)stage1_x3_lds_bytes(), static_cast<hipStream_t>(stream), a);
     return check_launch("salience_head_stage1_x3");
+}
+
+// sdetr_pyramid_flatten + sdetr_salience_head_hoist_x3 (enc_output given, no jobs) in ONE launch: the pyramid arguments of
+// the former (16-bit copies, mask and valid ratios are written; no fp32 outputs, no enc_in), the head arguments of the latter.
+extern "C" int sdetr_salience_head_hoist_pyramid_x3(
+    sdetr_stream_t stream, int num_levels, const float *const *feats, const float *const *pos, const uint8_t *const *masks,
+    const int *heights, const int *widths, const float *level_embeds, int batch_size, int channels, int spatial_size,
+    uint8_t *mask_out, void *feat_act, void *pos_act, float *valid_ratios, const void *enc_weight_x3, const float *enc_bias,
+    const float *enc_norm_weight, const float *enc_norm_bias, float enc_norm_eps, const float *norm_weight,
+    const void *weight_x3, float *memory_out, int64_t memory_batch_stride, float *g_out, int64_t g_batch_stride,
+    float *sigma_out, int64_t sigma_batch_stride)
+{
+    if (num_levels <= 0 || num_levels > kPyrMaxLevels) return fail("salience_head_hoist_pyramid_x3: 1..%d levels", kPyrMaxLevels);
+    if (channels != kC) return fail("salience_head_hoist_pyramid_x3: built for embed_dim = hidden_dim = %d (got %d)", kC, channels);
+    if (batch_size < 0 || spatial_size <= 0) return fail("salience_head_hoist_pyramid_x3: bad dims");
+    if (!feats || !pos || !masks || !heights || !widths || !level_embeds || !mask_out || !feat_act || !pos_act)
+        return fail("salience_head_hoist_pyramid_x3: null pointer");
+    if (!enc_weight_x3 || !enc_bias || !enc_norm_weight || !enc_norm_bias || !norm_weight || !weight_x3 || !g_out || !sigma_out)
+        return fail("salience_head_hoist_pyramid_x3: null pointer (head)");
+    if ((g_batch_stride % 4) || g_batch_stride < (int64_t)spatial_size * kC || sigma_batch_stride < spatial_size ||
+        (memory_out && ((memory_batch_stride % 4) || memory_batch_stride < (int64_t)spatial_size * kC)))
+        return fail("salience_head_hoist_pyramid_x3: bad output batch strides");
+    if (stage1_block_tokens(batch_size, spatial_size) != 32)
+        return fail("salience_head_hoist_pyramid_x3: 32-token blocks only (unset SDETR_HEAD_ROWTILES)");
+    PyramidSrc src{};
+    src.levels = num_levels;
+    int64_t start = 0;
+    for (int l = 0; l < num_levels; ++l) {
+        const int H = heights[l], W = widths[l];
+        if (H <= 0 || W <= 0 || !feats[l] || !pos[l] || !masks[l]) return fail("salience_head_hoist_pyramid_x3: bad level %d", l);
+        src.feat[l] = feats[l]; src.pos[l] = pos[l]; src.mask[l] = masks[l];
+        src.H[l] = H; src.W[l] = W; src.start[l] = (int)start;
+        src.box_wh[l] = 0.05f * (float)(1u << l);
+        start += (int64_t)H * W;
+        if (start > spatial_size || (int64_t)batch_size * kC * H * W > 0x7fffffffffffLL)
+            return fail("salience_head_hoist_pyramid_x3: sizes out of range");
+    }
+    if (start != spatial_size)
+        return fail("salience_head_hoist_pyramid_x3: spatial_size %d is not the pixel count %lld", spatial_size, (long long)start);
+    for (int l = num_levels; l <= kPyrMaxLevels; ++l) src.start[l] = spatial_size;
+    // a 32-token tile stages the geometry and the embeddings of up to kPyrTileLevels levels
+    for (int l = 0; l + kPyrTileLevels < num_levels; ++l)
+        if (src.start[l + kPyrTileLevels] / 32 == (src.start[l + 1] - 1) / 32)
+            return fail("salience_head_hoist_pyramid_x3: more than %d levels inside one 32-token tile", kPyrTileLevels);
+    if (batch_size == 0) return 0;
+    src.level_embed = level_embeds;
+    src.feat_act = reinterpret_cast<bf16_t *>(feat_act); src.pos_act = reinterpret_cast<bf16_t *>(pos_act);
+    src.mask_out = mask_out; src.valid_ratios = valid_ratios;
+    Stage1Args a;
+    a.x = nullptr; a.x_batch_stride = 0; a.x_row_stride = 0;
+    a.w_enc = reinterpret_cast<const float4 *>(enc_weight_x3);
+    a.b_enc = enc_bias; a.g_enc = enc_norm_weight; a.beta_enc = enc_norm_bias; a.eps_enc = enc_norm_eps;
+    a.row_scale = nullptr; a.coarse = nullptr; a.ch = a.cw = a.h = a.w = 0;
+    a.alpha = nullptr; a.g1 = norm_weight; a.beta1 = norm_weight; a.eps1 = 0.f;   // (beta1 / b1: staged, not used)
+    a.w1 = reinterpret_cast<const float4 *>(weight_x3); a.b1 = norm_weight;
+    a.memory_out = memory_out; a.mem_batch_stride = memory_batch_stride;
+    a.z_local = nullptr; a.partial = nullptr; a.n = spatial_size; a.nblk = (spatial_size + 31) / 32;
+    a.g_out = g_out; a.g_batch_stride = g_batch_stride; a.sigma_out = sigma_out; a.sigma_batch_stride = sigma_batch_stride;
+    if ((int64_t)a.nblk * batch_size > 0x7fffffff) return fail("salience_head_hoist_pyramid_x3: too many tiles");
+    static DeviceOnce lds_once;   // > 64 KiB of dynamic LDS has to be requested once per device
+    const int lds = kPyrLdsFloats * (int)sizeof(float);
+    allow_dynamic_lds(salience_head_hoist_pyramid_kernel, lds_once, lds);
+    hipLaunchKernelGGL(salience_head_hoist_pyramid_kernel, dim3((unsigned)(a.nblk * batch_size)), dim3(512), (size_t)lds,
+                       static_cast<hipStream_t>(stream), a, src, a.nblk);
+    return check_launch("salience_head_hoist_pyramid_x3");
 }
 
 // The per-image constant of layer2[0] on its own (sdetr_salience_head_stage2 launches it itself; a caller that puts stage

@@ -409,16 +409,46 @@ constexpr int kS2PlaneRow = kHalf * 2 + 16;            // 272 bytes
 constexpr int kS2PlaneBytes = 64 * kS2PlaneRow;        // 17 408
 constexpr int kS2Planes = 3 * kS2PlaneBytes;           // 52 224
 
+// ---- stage 1 straight from the pyramid (PYR form of stage1_x3_body) ---------------------------------------------------
+// The hoisted launch used to read enc_in = keep ? feat + (pos + level_embed) : 0 back from memory, 45.7 MB of fp32 rows
+// that pyramid_flatten_all_kernel (plumbing.hip) had written one launch earlier for this reader alone.  In the PYR form
+// the workgroup builds its 32 rows of enc_in itself from the fp32 NCHW maps -- the same keep rule, the same two fp32
+// additions, the same bits -- and writes what the flatten wrote for the REST of the step: the 16-bit copies of feat and
+// pos + level_embed, the flattened padding mask, the valid ratios.  Tiles are dealt over the flat token index of an image,
+// so a tile can straddle image rows and levels: every token row resolves its own level / y / x (one integer division per
+// row, by the 32 threads that also fetch the row's padding byte); the loads themselves need the offset inside the level only.
+constexpr int kPyrMaxLevels = 8;
+constexpr int kPyrTileLevels = 4;   // levels one 32-token tile may touch (the launcher checks)
+struct PyramidSrc {
+    const float *feat[kPyrMaxLevels], *pos[kPyrMaxLevels];   // fp32 [B, 256, H, W] per level
+    const uint8_t *mask[kPyrMaxLevels];                       // [B, H, W], non-zero = padding
+    int H[kPyrMaxLevels], W[kPyrMaxLevels], start[kPyrMaxLevels + 1];
+    float box_wh[kPyrMaxLevels];                              // 0.05 * 2^level (the proposal's box side)
+    const float *level_embed;                                 // [levels, 256]
+    int levels;
+    bf16_t *feat_act, *pos_act;                               // [B, S, 256] 16-bit activations
+    uint8_t *mask_out;                                        // [B, S]
+    float *valid_ratios;                                      // [B, levels, 2] (w, h) or NULL
+};
+// LDS of the PYR form (floats): feat tile | pos tile | parameter rows | srow | level embeddings | level geometry | row info
+constexpr int kPyrGeo = 8;          // per touched level: valid height, valid width, H, W, box_wh
+constexpr int kPyrLdsFloats = 2 * 32 * kXS + kParRows * kC + 32 + 4 + kPyrTileLevels * kC + kPyrTileLevels * kPyrGeo + 32 * 4;
+
 // (`blk` / `b` = token block and image: the kernel's own block indices, or the position inside a launch that also
 // carries other work -- fused_head_value.hip.  The first 512 threads of the workgroup take part.)
-__device__ __forceinline__ void stage1_x3_body(const Stage1Args &p, int blk, int b)
+template <bool PYR = false>
+__device__ __forceinline__ void stage1_x3_body(const Stage1Args &p, int blk, int b, const PyramidSrc *src = nullptr)
 {
     constexpr int TM = 32, THREADS = 512;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char *planes = reinterpret_cast<char *>(smem);               // three bf16 planes of the GEMM operand ...
     float *tile = smem;                                           // ... or the fp32 tile [TM][kXS] between the GEMMs
-    float *par = smem + kX3Region / 4;                            // [kParRows][kC]
+    float *par = smem + (PYR ? 2 * TM * kXS : kX3Region / 4);    // [kParRows][kC] (PYR: behind the feat and pos tiles)
     float *srow = par + kParRows * kC;                            // [TM] modulation factor, [TM] = alpha
+    float *tpos = smem + TM * kXS;                                // PYR: the position tile [TM][kXS] next to the feature tile
+    float *lemb = srow + TM + 4;                                  // PYR: [kPyrTileLevels][kC] level embeddings of the tile's levels
+    float *geo = lemb + kPyrTileLevels * kC;                      // PYR: [kPyrTileLevels][kPyrGeo]
+    int *rowinfo = reinterpret_cast<int *>(geo + kPyrTileLevels * kPyrGeo);   // PYR: [TM][4] level slot, x, y, padding
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t0 = blk * TM;
@@ -440,16 +470,73 @@ __device__ __forceinline__ void stage1_x3_body(const Stage1Args &p, int blk, int
     WeightStreamX3<kX3Depth> ws;
     ws.start(with_enc ? (const void *)p.w_enc : (const void *)p.w1, wave, lane);
 
+    int l0 = 0;   // PYR: level of the tile's first token
     // ---- token tile (split into planes when a GEMM consumes it directly), parameters and row factors -> LDS ----
     {
-        const float *xb = p.x + (int64_t)b * p.x_batch_stride + (int64_t)t0 * p.x_row_stride;
         constexpr int NL = TM * 64 / THREADS;   // float4 per thread
         float4 v[NL];
+        // PYR: lane = token (32 consecutive tokens of a channel are one 128-byte run of the NCHW map), 16 channels per thread
+        constexpr int NC = kC * TM / THREADS;
+        float pf[NC], pq[NC];
+        const int tok = tid & 31, cg = tid >> 5;
+        if (PYR) {
+            const PyramidSrc &s = *src;
+            for (int j = 1; j < s.levels; ++j) l0 += t0 >= s.start[j] ? 1 : 0;   // level of the tile's first token (uniform)
+            const int t = min(t0 + tok, p.n - 1);
+            int slot = 0, wl = s.W[l0], hw = s.H[l0] * s.W[l0], st = s.start[l0];
+            const float *fp = s.feat[l0], *pp = s.pos[l0];
+            const uint8_t *mp = s.mask[l0];
+#pragma unroll
+            for (int k = 1; k < kPyrTileLevels; ++k) {
+                const int l = min(l0 + k, s.levels - 1);
+                if (l0 + k < s.levels && t >= s.start[l]) {
+                    slot = k; wl = s.W[l]; hw = s.H[l] * s.W[l]; st = s.start[l];
+                    fp = s.feat[l]; pp = s.pos[l]; mp = s.mask[l];
+                }
+            }
+            const int tl = t - st;   // the token's pixel inside its level
+            const int64_t e0 = ((int64_t)b * kC + cg) * hw + tl;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) pf[i] = fp[e0 + (int64_t)(i * (THREADS / TM)) * hw];
+#pragma unroll
+            for (int i = 0; i < NC; ++i) pq[i] = pp[e0 + (int64_t)(i * (THREADS / TM)) * hw];
+            if (tid < TM) {   // the row's place in its level: the one division per token row
+                const int y = tl / wl;
+                *reinterpret_cast<int4 *>(rowinfo + 4 * tok) = make_int4(slot, tl - y * wl, y, (int)mp[(int64_t)b * hw + tl]);
+            }
+            // valid extents of the touched levels, recounted from column 0 / row 0 of the mask as the flatten does:
+            // wave 2k counts level l0 + k's height, wave 2k + 1 its width
+            {
+                const int l = l0 + (wave >> 1);
+                if (l < s.levels && s.start[l] < t0 + TM) {
+                    const int H = s.H[l], W = s.W[l];
+                    const uint8_t *mb = s.mask[l] + (int64_t)b * H * W;
+                    int cnt = 0;
+                    if (wave & 1) { for (int i = lane; i < W; i += 64) cnt += mb[i] == 0; }
+                    else          { for (int i = lane; i < H; i += 64) cnt += mb[(int64_t)i * W] == 0; }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+                    if (lane == 0) {
+                        float *g = geo + (wave >> 1) * kPyrGeo;
+                        g[wave & 1] = (float)cnt;
+                        if (!(wave & 1)) { g[2] = (float)H; g[3] = (float)W; g[4] = s.box_wh[l]; }
+                    }
+                }
+            }
+            if (tid >= 256) {   // the level embeddings of the tile's levels
+                const int l = l0 + ((tid - 256) >> 6), c4 = tid & 63;
+                if (l < s.levels)
+                    *reinterpret_cast<float4 *>(lemb + ((tid - 256) >> 6) * kC + c4 * 4) =
+                        *reinterpret_cast<const float4 *>(s.level_embed + (int64_t)l * kC + c4 * 4);
+            }
+        } else {
+        const float *xb = p.x + (int64_t)b * p.x_batch_stride + (int64_t)t0 * p.x_row_stride;
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int idx = tid + i * THREADS;
             const int r = idx >> 6, c4 = idx & 63;
             v[i] = *reinterpret_cast<const float4 *>(xb + (int64_t)min(r, nvalid - 1) * p.x_row_stride + c4 * 4);
+        }
         }
         if (tid < 256) {
             const int row = tid >> 6, c4 = tid & 63;
@@ -482,8 +569,15 @@ __device__ __forceinline__ void stage1_x3_body(const Stage1Args &p, int blk, int
             srow[tid] = s;
             if (tid == 0) srow[TM] = (p.row_scale || p.coarse) ? (p.alpha ? *p.alpha : 1.f) : 0.f;
         }
+        if (PYR) {   // the transposition: [channel][token] registers -> [token][channel] tiles
 #pragma unroll
-        for (int i = 0; i < NL; ++i) {
+            for (int i = 0; i < NC; ++i) {
+                tile[tok * kXS + cg + i * (THREADS / TM)] = pf[i];
+                tpos[tok * kXS + cg + i * (THREADS / TM)] = pq[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < (PYR ? 0 : NL); ++i) {
             const int idx = tid + i * THREADS;
             const int r = idx >> 6, c4 = idx & 63;
             const float4 val = r < nvalid ? v[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -501,6 +595,47 @@ __device__ __forceinline__ void stage1_x3_body(const Stage1Args &p, int blk, int
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     const long long sh_tile_done = clock64();   // (wave 0: its loads are back, its part of the tile is stored)
 #endif
+    if (PYR) {
+        // ---- rows: 16 threads per token, each 4 float4 of its channels (the LayerNorm phase's mapping): the flatten's outputs
+        // of the row, then enc_in's row -- (feat + (pos + level_embed)) * keep, pyramid_flatten_body's arithmetic -- into the planes
+        __syncthreads();
+        const PyramidSrc &s = *src;
+        const int r = tid >> 4, q = tid & 15;
+        const int4 ri = *reinterpret_cast<const int4 *>(rowinfo + 4 * r);   // level slot, x, y, padding
+        const float *g = geo + ri.x * kPyrGeo;
+        const float vh = g[0], vw = g[1], box_wh = g[4];
+        const bool pad = ri.w != 0;
+        const float cx = ((float)ri.y + 0.5f) / vw, cy = ((float)ri.z + 0.5f) / vh;
+        const bool keep = !pad && cx > 0.01f && cx < 0.99f && cy > 0.01f && cy < 0.99f && box_wh > 0.01f && box_wh < 0.99f;
+        const bool live = r < nvalid;
+        const int64_t o = ((int64_t)b * p.n + t0 + r) * kC + 4 * q;
+        float4 sum[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = 64 * i + 4 * q;
+            const float4 fv = *reinterpret_cast<const float4 *>(tile + r * kXS + c);
+            const float4 pv = *reinterpret_cast<const float4 *>(tpos + r * kXS + c);
+            const float4 e = *reinterpret_cast<const float4 *>(lemb + ri.x * kC + c);
+            const float4 qv = make_float4(pv.x + e.x, pv.y + e.y, pv.z + e.z, pv.w + e.w);
+            sum[i] = keep && live ? make_float4(fv.x + qv.x, fv.y + qv.y, fv.z + qv.z, fv.w + qv.w)
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) {
+                *reinterpret_cast<uint2 *>(s.feat_act + o + 64 * i) = make_uint2(pack_act2(fv.x, fv.y), pack_act2(fv.z, fv.w));
+                *reinterpret_cast<uint2 *>(s.pos_act + o + 64 * i) = make_uint2(pack_act2(qv.x, qv.y), pack_act2(qv.z, qv.w));
+            }
+        }
+        if (live && q == 0) {
+            s.mask_out[(int64_t)b * p.n + t0 + r] = pad ? 1 : 0;
+            if (s.valid_ratios && ri.y == 0 && ri.z == 0) {   // the level's first token: get_valid_ratios, (w, h)
+                float *vr = s.valid_ratios + ((int64_t)b * s.levels + l0 + ri.x) * 2;
+                vr[0] = vw / g[3];
+                vr[1] = vh / g[2];
+            }
+        }
+        __syncthreads();   // every thread holds its part of the two tiles: the planes may overwrite them
+#pragma unroll
+        for (int i = 0; i < 4; ++i) store_split<SH_SITE1_SOFT>(planes, r, 64 * i + 4 * q, sum[i]);
+    }
     __syncthreads();
     SH_STAMP();   // 1: tile, parameters, row factors in LDS
 
@@ -569,6 +704,10 @@ __device__ __forceinline__ void stage1_x3_body(const Stage1Args &p, int blk, int
             v[i] = ln_apply(v[i], mean, rstd, *reinterpret_cast<const float4 *>(par + kParG1 * kC + CS * i + 4 * q),
                             hoist ? make_float4(0.f, 0.f, 0.f, 0.f)
                                   : *reinterpret_cast<const float4 *>(par + kParBeta1 * kC + CS * i + 4 * q));
+        // (and the LDS queue is drained, nothing moved across, before the barrier: whatever the schedule in front of this
+        // point -- the PYR form changes it -- no LDS result is consumed behind a barrier it was requested in front of)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();   // every thread holds its part of the tile in registers: the planes may overwrite it
 #pragma unroll
         for (int i = 0; i < NV; ++i) store_split<SH_SITE2_SOFT>(planes, r, CS * i + 4 * q, v[i]);

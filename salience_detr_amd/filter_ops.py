@@ -626,6 +626,85 @@ def salience_head_hoist(x: Tensor, predictor, enc_output=None, enc_output_norm=N
     return HoistedHead(g, sigma, c0)
 
 
+# The pyramid flatten inside the hoisted stage-1 launch (csrc/salience_head_core.h, PYR form) where nothing but that launch
+# would read the flatten's fp32 ``enc_output`` input: 16-bit encoder, no fp32 / aux outputs wanted.  False = the flatten's
+# own launch followed by ``salience_head_hoist`` (same bits; the reference of tests/test_stage1_flatten_fused_gpu.py).
+FLATTEN_IN_STAGE1 = True
+_PYR_TILE_LEVELS = 4     # levels that may meet inside one 32-token tile (csrc/salience_head_core.h kPyrTileLevels)
+
+
+def hoist_pyramid_applies(multi_level_feats, multi_level_pos_embeds, multi_level_masks, predictor, enc_output, act) -> bool:
+    """Does ``salience_head_hoist_pyramid`` take this pyramid?  fp32 NCHW maps with 256 channels on one HIP device, a 16-bit
+    activation type, the fp32 256-wide head on the bf16x3 kernels, at most 8 levels of which at most 4 meet in a tile."""
+    feats, L = list(multi_level_feats), len(multi_level_feats)
+    if not (FLATTEN_IN_STAGE1 and salience_head_bf16x3 and _hip.is_act16(act) and 1 <= L <= 8):
+        return False
+    if any((not t.is_cuda) or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 256
+           for t in feats + list(multi_level_pos_embeds)):
+        return False
+    if any(m.dtype not in (torch.bool, torch.uint8) for m in multi_level_masks):
+        return False
+    if not (getattr(predictor, "h_dim", 0) == 256 and predictor.layer1[1].weight.dtype == torch.float32
+            and enc_output is not None and enc_output.weight.dtype == torch.float32 and enc_output.weight.is_cuda):
+        return False
+    starts = [0]
+    for f in feats:
+        starts.append(starts[-1] + int(f.shape[2]) * int(f.shape[3]))
+    return all(starts[l + _PYR_TILE_LEVELS] // 32 != (starts[l + 1] - 1) // 32 for l in range(L - _PYR_TILE_LEVELS))
+
+
+def salience_head_hoist_pyramid(multi_level_feats, multi_level_pos_embeds, multi_level_masks, level_embeds: Tensor, predictor,
+                                enc_output, enc_output_norm, act: torch.dtype, memory_out: Optional[Tensor] = None):
+    """``pyramid_flatten(want_bf16=act, want_fp32=False)`` and ``salience_head_hoist`` of its ``enc_output`` input in ONE launch
+    (include/salience_hip.h, sdetr_salience_head_hoist_pyramid_x3): the stage-1 tiles read the fp32 NCHW maps themselves.
+    Returns ``(HoistedHead, mask_flatten [B,S] bool, feat_act [B,S,256], pos_act [B,S,256], valid_ratios [B,L,2])`` -- the
+    same bits as the two launches.  No job rides on this launch: the pending ones read ``feat_act``."""
+    feats = [f.contiguous() for f in multi_level_feats]
+    pos = [p.contiguous() for p in multi_level_pos_embeds]
+    masks = [m.contiguous() for m in multi_level_masks]
+    _hip.require_device("salience_head_hoist_pyramid", level_embeds=level_embeds, **{f"feat{i}": f for i, f in enumerate(feats)},
+                        **{f"pos{i}": t for i, t in enumerate(pos)}, **{f"mask{i}": m for i, m in enumerate(masks)})
+    if not hoist_pyramid_applies(feats, pos, masks, predictor, enc_output, act):
+        raise RuntimeError("salience_head_hoist_pyramid: fp32 [B,256,H,W] maps, a 16-bit activation type and the fp32 256-wide "
+                           "head on the bf16x3 kernels expected (at most 8 levels, at most 4 inside one 32-token tile)")
+    L = len(feats)
+    B, C = feats[0].shape[:2]
+    for f, q, m in zip(feats, pos, masks):
+        if q.shape != f.shape or tuple(m.shape) != (B, f.shape[2], f.shape[3]) or f.shape[:2] != (B, C):
+            raise RuntimeError("salience_head_hoist_pyramid: feature / position / mask shapes of a level disagree")
+    S = sum(int(f.shape[2]) * int(f.shape[3]) for f in feats)
+    dev = feats[0].device
+    mask_out = torch.empty((B, S), dtype=torch.bool, device=dev)
+    feat_act = torch.empty((B, S, C), dtype=act, device=dev)
+    pos_act = torch.empty((B, S, C), dtype=act, device=dev)
+    valid_ratios = torch.empty((B, L, 2), dtype=torch.float32, device=dev)
+    le = level_embeds.detach().float().contiguous()
+    g = torch.empty((B, S, C), dtype=torch.float32, device=dev)
+    sigma = torch.empty((B, S), dtype=torch.float32, device=dev)
+    mbs = 0
+    if memory_out is not None:
+        if memory_out.shape != g.shape or memory_out.stride(2) != 1 or memory_out.stride(1) != C or memory_out.dtype != torch.float32:
+            raise RuntimeError("salience_head_hoist_pyramid: memory_out must be fp32 [B,S,C] with contiguous rows")
+        mbs = memory_out.stride(0)
+    l1n, l1 = predictor.layer1[0], predictor.layer1[1]
+    c0 = _layer1_constant(predictor)
+    mu8s = [m.view(torch.uint8) if m.dtype == torch.bool else m for m in masks]
+    ptrs = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
+    ints = lambda vs: (ctypes.c_int * L)(*vs)
+    lib = _hip.lib(act)
+    with torch.cuda.device(dev):
+        code = lib.sdetr_salience_head_hoist_pyramid_x3(
+            _hip.stream_ptr(), L, ptrs(feats), ptrs(pos), ptrs(mu8s), ints([int(f.shape[2]) for f in feats]),
+            ints([int(f.shape[3]) for f in feats]), le.data_ptr(), B, C, S, mask_out.data_ptr(), feat_act.data_ptr(),
+            pos_act.data_ptr(), valid_ratios.data_ptr(), packed_linear_weight(enc_output.weight, split3=True).data_ptr(),
+            enc_output.bias.detach().data_ptr(), enc_output_norm.weight.detach().data_ptr(),
+            enc_output_norm.bias.detach().data_ptr(), float(enc_output_norm.eps), l1n.weight.data_ptr(),
+            packed_linear_weight(l1.weight, split3=True).data_ptr(), _hip.ptr(memory_out), mbs, g.data_ptr(), g.stride(0),
+            sigma.data_ptr(), sigma.stride(0))
+    _hip.check(code, "salience_head_hoist_pyramid")
+    return HoistedHead(g, sigma, c0), mask_out, feat_act, pos_act, valid_ratios
+
+
 def salience_head(x: Tensor, predictor, row_scale: Optional[Tensor] = None, coarse_score: Optional[Tensor] = None,
                   level_hw=None, alpha: Optional[Tensor] = None, enc_output=None, enc_output_norm=None,
                   memory_out: Optional[Tensor] = None, score_flat: Optional[Tensor] = None,

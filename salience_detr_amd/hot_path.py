@@ -118,7 +118,21 @@ class SalienceEncoderHotPath(nn.Module):
         native = not (torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
                                                    or any(f.requires_grad for f in multi_level_feats)))
         feat_enc = pos_enc = None
-        if native and multi_level_feats[0].dtype == torch.float32:
+        hoisted_head = None
+        from . import filter_ops, salience_filtering as _sf
+        # The hoisted stage 1 of the salience head is the only reader of the flatten's fp32 enc_output input when the encoder
+        # runs in 16 bits and nobody asks for the fp32 tensors: its tiles then read the pyramid themselves and write the
+        # flatten's other outputs (one launch and a 45.7 MB round trip less at 2 x 800 x 1333).  No job may ride on that launch
+        # (they read feat_enc, which it writes): the value projection rides on stage-2 launches, the finalize pass on the merge.
+        if (native and not return_aux and multi_level_feats[0].dtype == torch.float32 and _sf.HOIST_HEAD
+                and not _sf.HOIST_CARRIES_VALUE and _sf.FINALIZE_LEVEL is not None
+                and filter_ops.hoist_pyramid_applies(multi_level_feats, multi_level_pos_embeds, multi_level_masks,
+                                                     self.enc_mask_predictor, self.enc_output, edt)):
+            enc_in = feat_flatten = lvl_pos_embed_flatten = None
+            hoisted_head, mask_flatten, feat_enc, pos_enc, valid_ratios_k = filter_ops.salience_head_hoist_pyramid(
+                multi_level_feats, multi_level_pos_embeds, multi_level_masks, self.level_embeds, self.enc_mask_predictor,
+                self.enc_output, self.enc_output_norm, edt)
+        elif native and multi_level_feats[0].dtype == torch.float32:
             # F0 in one launch per level (flatten + level embedding + validity mask [+ bf16 copies])
             from .filter_ops import pyramid_flatten
             feat_flatten, lvl_pos_embed_flatten, enc_in, mask_flatten, feat_enc, pos_enc, valid_ratios_k = pyramid_flatten(
@@ -160,8 +174,8 @@ class SalienceEncoderHotPath(nn.Module):
             starts.append(starts[-1] + h * w)
 
         # the no-grad path keeps enc_output + enc_output_norm inside the salience-head kernel
-        fuse_enc = (enc_in is not None and self.enc_mask_predictor.fused_kernels_apply(enc_in)
-                    and self.enc_output.weight.dtype == torch.float32)
+        fuse_enc = hoisted_head is not None or (enc_in is not None and self.enc_mask_predictor.fused_kernels_apply(enc_in)
+                                                and self.enc_output.weight.dtype == torch.float32)
         backbone_output_memory = None
         if fuse_enc:
             if return_aux:
@@ -194,9 +208,10 @@ class SalienceEncoderHotPath(nn.Module):
         if fuse_enc:
             score_flat = torch.empty(mask_flatten.shape, dtype=torch.float32, device=mask_flatten.device)
             salience_score, level_inds, level_score = level_filtering(
-                enc_in, mask_flatten, level_shapes, starts, level_token_nums, self.enc_mask_predictor, self.alpha,
-                enc_output=self.enc_output, enc_output_norm=self.enc_output_norm, memory_out=backbone_output_memory,
-                score_flat=score_flat, extras=extras, value_jobs=value_jobs, finalize_job=finalize_job)
+                enc_in if hoisted_head is None else hoisted_head.g, mask_flatten, level_shapes, starts, level_token_nums,
+                self.enc_mask_predictor, self.alpha, enc_output=self.enc_output, enc_output_norm=self.enc_output_norm,
+                memory_out=backbone_output_memory, score_flat=score_flat, extras=extras, value_jobs=value_jobs,
+                finalize_job=finalize_job, hoisted=hoisted_head)
         else:
             salience_score, level_inds, level_score = level_filtering(
                 backbone_output_memory, mask_flatten, level_shapes, starts, level_token_nums, self.enc_mask_predictor,

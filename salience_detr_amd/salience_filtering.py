@@ -197,7 +197,8 @@ def level_filtering(backbone_output_memory: Tensor, mask_flatten: Tensor, level_
                     level_start_index: Sequence[int], level_token_nums: Sequence[int], mask_predictor: nn.Module,
                     alpha: Tensor, enc_output: Optional[nn.Module] = None, enc_output_norm: Optional[nn.Module] = None,
                     memory_out: Optional[Tensor] = None, score_flat: Optional[Tensor] = None,
-                    extras: Optional[dict] = None, value_jobs: Optional[list] = None, finalize_job=None):
+                    extras: Optional[dict] = None, value_jobs: Optional[list] = None, finalize_job=None,
+                    hoisted=None):
     """Coarse-to-fine salience scores + per-level top-k (salience_transformer.py:123-154).
 
     ``level_shapes`` / ``level_start_index`` / ``level_token_nums`` are python ints (shapes come from the
@@ -215,6 +216,9 @@ def level_filtering(backbone_output_memory: Tensor, mask_flatten: Tensor, level_
     launches of the two coarsest levels (few workgroups on an otherwise empty chip) carry one each -- stage 1, then
     stage 2 -- coarsest level first.  ``finalize_job``: the pending token-space pass of the encoder's output
     (``filter_ops.FinalizeJob``); the first stage-1 launch without a value job carries it.
+    ``hoisted``: the ``filter_ops.HoistedHead`` of ALL levels' tokens when the caller has launched the hoisted stage 1
+    already (``filter_ops.salience_head_hoist_pyramid``, which reads the pyramid itself: no ``enc_output`` input exists
+    then, and the first argument is only looked at for its shape -- ``hoisted.g`` serves).
     """
     B = backbone_output_memory.shape[0]
     L = len(level_shapes)
@@ -240,8 +244,9 @@ def level_filtering(backbone_output_memory: Tensor, mask_flatten: Tensor, level_
         offs = [sum(ks[:i]) for i in range(L)]
         sel_score = torch.empty((B, sum(ks)), dtype=torch.float32, device=dev)
         sel_inds = torch.empty((B, sum(ks)), dtype=torch.int64, device=dev)
-    hoisted = None
-    if fused and HOIST_HEAD and filter_ops.salience_head_bf16x3:
+    if hoisted is not None and not fused:
+        raise RuntimeError("level_filtering: a hoisted head needs the no-grad fp32 256-wide MaskPredictor path")
+    if hoisted is None and fused and HOIST_HEAD and filter_ops.salience_head_bf16x3:
         pending = [j for j in (value_jobs or ()) if not j.done]
         hoisted = salience_head_hoist(backbone_output_memory, mask_predictor, enc_output=enc_output,
                                       enc_output_norm=enc_output_norm, memory_out=memory_out,
