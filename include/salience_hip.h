@@ -1303,6 +1303,71 @@ int sdetr_backbone_resize_batch_images(sdetr_stream_t stream, const void *const 
                                        float *canvas, uint8_t *mask);
 
 /* ---------------------------------------------------------------------------------------------
+ * Backbone backward (training the ResNet, csrc/backbone_backward.hip): the gradients of the conv ops above, for
+ * kernel 1 or 3, stride 1 or 2, padding (kernel - 1) / 2, in_channels % 32 == 0, out_channels % 8 == 0, channels-last
+ * activations; precision as above (0: fp32 activations and gradients, products at fp32 accuracy; 1: 16-bit activations
+ * and activation gradients, one product, fp32 accumulation).  Weight gradients are f32 in both.  No atomics anywhere:
+ * two runs are bit-identical.  Every launch writes every element of its output (no memset is ever needed).
+ *
+ * For y = relu?(conv(x, w') + b' (+ residual)), w' = w * s[out], s = gamma / sqrt(var + eps), `dz` is the gradient at the
+ * op's pre-activation, channels-last [batch, Ho, Wo, out_channels] in the compute dtype.
+ *
+ * sdetr_backbone_pack_dgrad: w' in the backward-data reduction order, 16-bit planes [planes][in][k * k * O32] with
+ * reduction index (ky * k + kx) * O32 + o (O32 = out_channels rounded up to 32, zero columns past out_channels; planes as
+ * sdetr_backbone_pack), sdetr_backbone_dgrad_packed_bytes long; scale f32 [out] = s.  packed may be NULL: only the scale.
+ *
+ * sdetr_backbone_bwd_op, by kind:
+ *   0 dgrad:  out [batch, height, width, in_channels] (compute dtype) = dx[n, iy, ix, ci] = sum over (ky, kx, co) of
+ *             dz[n, oy, ox, co] * w'[co, ky, kx, ci] for the taps where iy + padding - ky and ix + padding - kx are
+ *             multiples of the stride, then (dx (+ add)) * (mask > 0)?: add (or NULL) is a gradient shaped as out that
+ *             another consumer of the same tensor has produced, mask (or NULL) the stored output of the op that produced
+ *             the tensor (its ReLU backward).  weight = sdetr_backbone_pack_dgrad's planes.  Stride 2 is decomposed by
+ *             input parity (no zero is multiplied; a 1x1 stride-2 op writes exact zeros, before add, off the even pixels).
+ *   1 wgrad:  out f32 [out_channels, in_channels, k, k] = s[co] * sum over (n, oy, ox) of dz[n, oy, ox, co] *
+ *             x[n, oy * stride + ky - padding, ox * stride + kx - padding, ci]; x = the op's input [batch, height, width,
+ *             in_channels] (compute dtype), scale = s.
+ *   2 ingest: dz = the f32 NCHW cotangent [batch, in_channels, height, width] of a returned map; out channels-last
+ *             [batch, height, width, in_channels] (compute dtype) = (dz (+ add)) * (mask > 0)?.
+ * height / width are always the conv's INPUT size.  splits: 0 = automatic, n > 0 = n pieces of the reduction (clamped; the
+ * (tap, out channel) steps of a dgrad, the 32-pixel steps of a wgrad), summed in a fixed order through the workspace.
+ * sdetr_backbone_bwd_splits: the resolved count.  sdetr_backbone_bwd_workspace_bytes: the largest piece buffer of a plan.
+ * sdetr_backbone_dgrad / _wgrad run one op; sdetr_backbone_bwd_run a whole plan in order, validated before the first
+ * launch.  dz, x and weight 16-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_backbone_bwd_op {
+    int kind;
+    const void *dz;
+    const void *x;
+    const void *weight;
+    const float *scale;
+    const void *add;
+    const void *mask;
+    void *out;
+    int batch;
+    int in_channels;
+    int height;
+    int width;
+    int out_channels;
+    int kernel_size;
+    int stride;
+    int padding;
+    int splits;
+} sdetr_backbone_bwd_op;
+
+int64_t sdetr_backbone_dgrad_packed_bytes(int out_channels, int in_channels, int kernel_size, int precision);
+int sdetr_backbone_pack_dgrad(sdetr_stream_t stream, const float *weight, const float *gamma, const float *running_var,
+                              float eps, int out_channels, int in_channels, int kernel_size, int precision, void *packed,
+                              float *scale);
+int sdetr_backbone_bwd_splits(const sdetr_backbone_bwd_op *op, int precision);
+int64_t sdetr_backbone_bwd_workspace_bytes(const sdetr_backbone_bwd_op *ops, int n_ops, int precision);
+int sdetr_backbone_dgrad(sdetr_stream_t stream, const sdetr_backbone_bwd_op *op, int precision, void *workspace,
+                         int64_t workspace_bytes);
+int sdetr_backbone_wgrad(sdetr_stream_t stream, const sdetr_backbone_bwd_op *op, int precision, void *workspace,
+                         int64_t workspace_bytes);
+int sdetr_backbone_bwd_run(sdetr_stream_t stream, const sdetr_backbone_bwd_op *ops, int n_ops, int precision,
+                           void *workspace, int64_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.
  *
  * sdetr_cdn_queries: ONE launch.  boxes f32 [batch * capacity, 4] (cx, cy, w, h in [0, 1]), labels int32

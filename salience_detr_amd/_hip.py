@@ -81,6 +81,15 @@ class BackboneOpStruct(ctypes.Structure):
                 ("batch", ctypes.c_int), ("in_channels", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int),
                 ("out_channels", ctypes.c_int), ("kernel_size", ctypes.c_int), ("stride", ctypes.c_int),
                 ("padding", ctypes.c_int), ("relu", ctypes.c_int), ("x_nchw", ctypes.c_int), ("splits", ctypes.c_int)]
+
+
+class BackboneBwdOpStruct(ctypes.Structure):
+    """``sdetr_backbone_bwd_op`` of include/salience_hip.h."""
+    _fields_ = [("kind", ctypes.c_int), ("dz", ctypes.c_void_p), ("x", ctypes.c_void_p), ("weight", ctypes.c_void_p),
+                ("scale", ctypes.c_void_p), ("add", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("batch", ctypes.c_int), ("in_channels", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int),
+                ("out_channels", ctypes.c_int), ("kernel_size", ctypes.c_int), ("stride", ctypes.c_int),
+                ("padding", ctypes.c_int), ("splits", ctypes.c_int)]
 _i64 = ctypes.c_int64
 _p = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -243,6 +252,13 @@ SIGNATURES = {
     "sdetr_backbone_conv": (_i, [_p, _p, _i, _p, _i64]),
     "sdetr_backbone_maxpool": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "sdetr_backbone_run": (_i, [_p, _p, _i, _i, _p, _i64]),
+    "sdetr_backbone_dgrad_packed_bytes": (_i64, [_i, _i, _i, _i]),
+    "sdetr_backbone_pack_dgrad": (_i, [_p] * 4 + [ctypes.c_float] + [_i] * 4 + [_p, _p]),
+    "sdetr_backbone_bwd_splits": (_i, [_p, _i]),
+    "sdetr_backbone_bwd_workspace_bytes": (_i64, [_p, _i, _i]),
+    "sdetr_backbone_dgrad": (_i, [_p, _p, _i, _p, _i64]),
+    "sdetr_backbone_wgrad": (_i, [_p, _p, _i, _p, _i64]),
+    "sdetr_backbone_bwd_run": (_i, [_p, _p, _i, _i, _p, _i64]),
     "sdetr_backbone_batch_images": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "sdetr_backbone_batch_images_ex": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "sdetr_backbone_resize_images": (_i, [_p, _p, _p, _p, _i, _i, _p]),

@@ -18,12 +18,21 @@ How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/
   * ``set_dtype``: fp32 (default) multiplies at fp32 accuracy (exact three-way bf16 split of both operands); bf16 /
     fp16 take one 16-bit product with fp32 accumulation and keep the activations in that type between layers.
 The HIP path serves every ``groups == 1`` arch without dilation or DCN: resnet18/34/50/101/152 and wide_resnet50_2 /
-101_2.  Grouped ResNeXt, and every call with grad enabled on something that requires grad, take the plain-torch composite
-(``F.conv2d`` + the frozen affine), which is also the autograd path: training the backbone in HIP is out of scope.  A
-CPU tensor on the HIP form raises: the hot path has no CPU fallback.
+101_2.  Grouped ResNeXt, and by default every call with grad enabled on something that requires grad, take the
+plain-torch composite (``F.conv2d`` + the frozen affine), which is also the default autograd path.  A CPU tensor on the
+HIP form raises: the hot path has no CPU fallback.
+
+Training in HIP (``set_train_form("hip")``, ``csrc/backbone_backward.hip``): a forward that needs autograd runs the same
+forward plan inside one autograd node; its backward is one ``sdetr_backbone_bwd_run`` call over ``build_backward_plan``:
+one backward-data launch per conv whose input has a trainable conv upstream, one backward-weight launch per trainable
+conv (plus the fixed-order reduction where a reduction is split), one ingest launch per returned map.  The stored
+activations are the ReLU masks and the weight-gradient operands; no activation is copied.  Served: ``hip_form()``
+archs with a frozen stem (``freeze_indices`` non-empty), an input without gradient, float32 or bfloat16; anything else
+raises at forward.  Stem / max-pool backward and float16 training are out of scope.
 """
 import ctypes
 import os
+import weakref
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Type, Union
 
 import torch
@@ -243,6 +252,7 @@ class ResNetBackbone(nn.Module):
         self.dilation = net.dilation
         self.num_channels = [64 * self.block.expansion * 2 ** i for i in self.return_indices]
         self.compute_dtype = torch.float32
+        self.train_form = "torch"
         if weights is not None:
             self.load_weights(weights)
         if len(freeze_indices) > 0:
@@ -311,6 +321,8 @@ class ResNetBackbone(nn.Module):
 
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, x: Tensor) -> Dict[str, Tensor]:
+        if self.train_form == "hip" and self._needs_autograd(x):
+            return self.forward_hip_train(x)
         if self._needs_autograd(x) or not self.hip_form():
             return self.forward_torch(x)
         return self.forward_hip(x)
@@ -350,9 +362,12 @@ class ResNetBackbone(nn.Module):
         return derived(conv, "backbone_packed", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build,
                        extra=(float(bn.eps), precision, self.compute_dtype, layout))
 
-    def build_plan(self, x: Tensor, splits: int = 0):
+    def build_plan(self, x: Tensor, splits: int = 0, acts: Optional[Dict[str, Tensor]] = None):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep)`` where
-        ``outputs`` are the returned fp32 NCHW maps and ``keep`` every tensor the plan points into."""
+        ``outputs`` are the returned fp32 NCHW maps and ``keep`` every tensor the plan points into.  ``acts`` (a dict)
+        receives the channels-last output of every op under the op's name (``"conv1"``, ``"pool"``,
+        ``"layer2.0.conv1"``, ``"layer2.0.downsample.0"`` ..), in op order: what the training backward reads."""
+        names = {id(m): n for n, m in self.named_modules() if isinstance(m, nn.Conv2d)}
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
         dev, batch = x.device, x.shape[0]
         ops: List[_hip.BackboneOpStruct] = []
@@ -365,6 +380,8 @@ class ResNetBackbone(nn.Module):
             packed, bias = self._packed(conv, bn, 1 if x_nchw else 0)
             out = torch.empty(batch, ho, wo, conv.out_channels, device=dev, dtype=act)
             keep.extend((packed, bias, out))
+            if acts is not None:
+                acts[names[id(conv)]] = out
             ops.append(_hip.BackboneOpStruct(0, src.data_ptr(), packed.data_ptr(), bias.data_ptr(), _hip.ptr(residual),
                                              out.data_ptr(), _hip.ptr(nchw_out), batch, conv.in_channels, h, w,
                                              conv.out_channels, k, s, p, 1 if relu else 0, 1 if x_nchw else 0, splits))
@@ -375,6 +392,8 @@ class ResNetBackbone(nn.Module):
         ho, wo = _out_hw(h, 3, 2, 1), _out_hw(w, 3, 2, 1)
         pooled = torch.empty(batch, ho, wo, 64, device=dev, dtype=act)
         keep.append(pooled)
+        if acts is not None:
+            acts["pool"] = pooled
         ops.append(_hip.BackboneOpStruct(1, y.data_ptr(), None, None, None, pooled.data_ptr(), None, batch, 64, h, w, 64,
                                          3, 2, 1, 0, 0, 0))
         y, h, w = pooled, ho, wo
@@ -402,7 +421,7 @@ class ResNetBackbone(nn.Module):
     def _block_out_channels(blk) -> int:
         return blk.conv3.out_channels if isinstance(blk, Bottleneck) else blk.conv2.out_channels
 
-    def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+    def forward_hip(self, x: Tensor, splits: int = 0, acts: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
         if x.dtype != torch.float32:
             x = x.float()
         _hip.require_device("ResNetBackbone", x=x)
@@ -410,7 +429,7 @@ class ResNetBackbone(nn.Module):
             _hip.require_device("ResNetBackbone", parameter=t.detach())
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"ResNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
-        ops, outputs, keep = self.build_plan(x, splits)
+        ops, outputs, keep = self.build_plan(x, splits, acts)
         lib, precision = self._lib(), self._precision()
         arr = (_hip.BackboneOpStruct * len(ops))(*ops)
         ws_bytes = lib.sdetr_backbone_workspace_bytes(arr, len(ops), precision)
@@ -420,6 +439,234 @@ class ResNetBackbone(nn.Module):
         _hip.check(lib.sdetr_backbone_run(_hip.stream_ptr(), arr, len(ops), precision, ws.data_ptr(), ws_bytes),
                    "ResNetBackbone (run)", lib)
         return outputs
+
+    # ------------------------------------------------------------------------------------------ training in HIP
+    def set_train_form(self, form: str):
+        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
+        (the HIP forward plan inside an autograd node whose backward is one ``sdetr_backbone_bwd_run`` call, see
+        ``forward_hip_train``).  ``"hip"`` on a module or input that is not eligible (``hip_train_reason``) raises at
+        forward: it never falls back."""
+        if form not in ("torch", "hip"):
+            raise ValueError(f"ResNetBackbone.set_train_form: {form!r} is not 'torch' / 'hip'")
+        self.train_form = form
+        return self
+
+    def hip_train_reason(self, x: Optional[Tensor] = None) -> Optional[str]:
+        """Why the ``"hip"`` training form cannot serve this module (and input ``x``); ``None`` when it can."""
+        if not self.hip_form():
+            return "the architecture is not one the HIP kernels serve (grouped / dilated convs, a bias or a norm layer " \
+                   "other than FrozenBatchNorm2d)"
+        if any(p.requires_grad for p in list(self.conv1.parameters()) + list(self.bn1.parameters())):
+            return "the stem (conv1) is not frozen: the stem and max-pool backward are out of scope"
+        if self.compute_dtype not in (torch.float32, torch.bfloat16):
+            return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
+        if x is not None and x.requires_grad:
+            return "the input requires a gradient: the gradient to the image is out of scope"
+        return None
+
+    def hip_train_form(self, x: Optional[Tensor] = None) -> bool:
+        """True when ``set_train_form("hip")`` can train this module (on input ``x``): ``hip_form()``, a frozen stem, an
+        input without gradient and a float32 / bfloat16 compute dtype."""
+        return self.hip_train_reason(x) is None
+
+    def _blocks(self, height: int, width: int):
+        """Every residual block in forward order with its convs ``(name, conv, bn, in_h, in_w)``, its input tensor's name
+        and whether that input needs a gradient (a trainable conv lies upstream of it)."""
+        h, w = _out_hw(_out_hw(height, 7, 2, 3), 3, 2, 1), _out_hw(_out_hw(width, 7, 2, 3), 3, 2, 1)
+        src, needs, src_returned = "pool", self.conv1.weight.requires_grad, False
+        blocks = []
+        for i, stage in enumerate(self.stages()):
+            for j, blk in enumerate(stage):
+                prefix = f"layer{i + 1}.{j}"
+                chain, ch, cw = [], h, w
+                for n in ("conv1", "conv2", "conv3") if isinstance(blk, Bottleneck) else ("conv1", "conv2"):
+                    conv = getattr(blk, n)
+                    chain.append((f"{prefix}.{n}", conv, getattr(blk, "bn" + n[-1]), ch, cw))
+                    ch, cw = (_out_hw(v, conv.kernel_size[0], conv.stride[0], conv.padding[0]) for v in (ch, cw))
+                ds = None if blk.downsample is None else (f"{prefix}.downsample.0", blk.downsample[0], blk.downsample[1], h, w)
+                returned = i in self.return_indices and j == len(stage) - 1
+                blocks.append(dict(chain=chain, ds=ds, input=src, input_needs=needs, input_returned=src_returned,
+                                   returned=f"layer{i + 1}" if returned else None, out_hw=(ch, cw)))
+                needs = needs or any(c[1].weight.requires_grad for c in chain + ([ds] if ds else []))
+                src, src_returned, h, w = chain[-1][0], returned, ch, cw
+        return blocks
+
+    def build_backward_plan(self, batch: int, height: int, width: int) -> List[dict]:
+        """The backward of one forward on a ``[batch, 3, height, width]`` canvas as host data (no library, no tensors):
+        dicts ``kind`` (``"ingest"`` / ``"wgrad"`` / ``"dgrad"``), ``conv`` (the module name, or the stage for an ingest),
+        the operand NAMES ``dz``, ``x``, ``add``, ``mask``, ``out`` and the shape fields of ``sdetr_backbone_bwd_op``.
+        Names: a stored activation is called after the op that wrote it (``"layer2.0.conv1"``, ``"pool"``); ``"cot:layerN"``
+        is a returned map's incoming gradient, ``"dz:<op>"`` the gradient at that op's pre-activation, ``"raw:<op>"`` the
+        unmasked gradient of a returned stage's output arriving from the next stage (its ingest adds and masks it),
+        ``"tmp:<op>"`` a downsample branch's input gradient (the ``add`` of the block's first conv), ``"dw:<op>"`` the
+        weight gradient.  One wgrad per trainable conv, one dgrad per conv whose input has a trainable conv upstream, one
+        ingest per returned stage."""
+        plan: List[dict] = []
+        pending: Dict[str, str] = {}   # returned tensor -> the raw gradient the next stage produced
+
+        def op(kind, rec, **names):
+            name, conv, _, h, w = rec
+            d = dict(kind=kind, conv=name, dz=None, x=None, add=None, mask=None, out=None, batch=batch,
+                     in_channels=conv.in_channels, height=h, width=w, out_channels=conv.out_channels,
+                     kernel_size=conv.kernel_size[0], stride=conv.stride[0], padding=conv.padding[0])
+            d.update(names)
+            plan.append(d)
+
+        for blk in reversed(self._blocks(height, width)):
+            chain, ds = blk["chain"], blk["ds"]
+            out_name = chain[-1][0]
+            trainable = any(c[1].weight.requires_grad for c in chain + ([ds] if ds else []))
+            if blk["returned"] is not None and (trainable or blk["input_needs"]):
+                channels = chain[-1][1].out_channels
+                plan.append(dict(kind="ingest", conv=blk["returned"], dz="cot:" + blk["returned"], x=None,
+                                 add=pending.get(out_name), mask=out_name, out="dz:" + out_name, batch=batch,
+                                 in_channels=channels, height=blk["out_hw"][0], width=blk["out_hw"][1],
+                                 out_channels=channels, kernel_size=1, stride=1, padding=0))
+            if not (trainable or blk["input_needs"]):
+                break   # nothing at or below this block has a trainable conv
+            cur = "dz:" + out_name
+            if ds is not None and ds[1].weight.requires_grad:
+                op("wgrad", ds, dz=cur, x=blk["input"], out="dw:" + ds[0])
+            for idx in reversed(range(len(chain))):
+                rec = chain[idx]
+                src = blk["input"] if idx == 0 else chain[idx - 1][0]
+                if rec[1].weight.requires_grad:
+                    op("wgrad", rec, dz=cur, x=src, out="dw:" + rec[0])
+                if idx == 0:
+                    if blk["input_needs"]:
+                        add = "dz:" + out_name   # the identity branch
+                        if ds is not None:
+                            add = "tmp:" + ds[0]
+                            op("dgrad", ds, dz="dz:" + out_name, out=add)
+                        if blk["input_returned"]:
+                            pending[src] = "raw:" + src
+                            op("dgrad", rec, dz=cur, add=add, out="raw:" + src)
+                        else:
+                            op("dgrad", rec, dz=cur, add=add, mask=src, out="dz:" + src)
+                elif blk["input_needs"] or any(c[1].weight.requires_grad for c in chain[:idx]):
+                    op("dgrad", rec, dz=cur, mask=src, out="dz:" + src)
+                    cur = "dz:" + src
+                else:
+                    break
+        return plan
+
+    def _packed_dgrad(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d, with_weight: bool) -> Tuple[Optional[Tensor], Tensor]:
+        """``(backward-data packed weight, s[out])`` of ``conv`` + ``bn`` (``sdetr_backbone_pack_dgrad``), built once per
+        parameter version, precision and compute dtype; without ``with_weight`` only the scale."""
+        precision, lib = self._precision(), self._lib()
+        co, ci, k = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+
+        def build():
+            f32 = [t.detach().to(torch.float32).contiguous() for t in (conv.weight, bn.weight, bn.running_var)]
+            packed = None
+            if with_weight:
+                nbytes = lib.sdetr_backbone_dgrad_packed_bytes(co, ci, k, precision)
+                packed = torch.empty(nbytes // 2, dtype=torch.int16, device=f32[0].device)
+            scale = torch.empty(co, dtype=torch.float32, device=f32[0].device)
+            _hip.check(lib.sdetr_backbone_pack_dgrad(_hip.stream_ptr(), *[t.data_ptr() for t in f32], float(bn.eps), co, ci,
+                                                     k, precision, _hip.ptr(packed), scale.data_ptr()),
+                       "ResNetBackbone (pack dgrad)", lib)
+            return packed, scale
+        return derived(conv, "backbone_packed_dgrad" if with_weight else "backbone_bn_scale",
+                       (conv.weight, bn.weight, bn.running_var), build, extra=(float(bn.eps), precision, self.compute_dtype))
+
+    def _trainable_convs(self) -> List[Tuple[str, nn.Conv2d]]:
+        return [(n, m) for n, m in self.named_modules() if isinstance(m, nn.Conv2d) and m.weight.requires_grad]
+
+    def forward_hip_train(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+        """The ``"hip"`` training form: the HIP forward plan as one autograd node.  The node keeps the plan's channels-last
+        activations (no copy); its backward runs ``build_backward_plan`` with one ``sdetr_backbone_bwd_run`` call and
+        returns the fp32 weight gradients to autograd, which accumulates them into ``.grad``."""
+        reason = self.hip_train_reason(x)
+        if reason is not None:
+            raise RuntimeError(f"ResNetBackbone: the 'hip' training form cannot run: {reason}")
+        named = self._trainable_convs()
+        maps = _BackboneTrainFunction.apply(self, x, splits, tuple(n for n, _ in named), *[m.weight for _, m in named])
+        return dict(zip([f"layer{i + 1}" for i in sorted(self.return_indices)], maps))
+
+    def saved_activations(self) -> List[Tuple[str, Tensor]]:
+        """Test hook (read-only): ``(op name, post-activation output [B, H, W, C] in the compute dtype)`` of every op with
+        a ReLU, in op order (the stem first), as stored by the last ``"hip"`` training forward.  Valid while that
+        forward's autograd graph is alive."""
+        acts = self.__dict__.get("_train_acts")
+        acts = acts() if acts is not None else None
+        if acts is None:
+            raise RuntimeError("ResNetBackbone.saved_activations: no 'hip' training forward is alive")
+        return [(n, t) for n, t in acts.items() if n != "pool" and ".downsample." not in n]
+
+    def _run_backward(self, acts: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
+                      ) -> Dict[str, Tensor]:
+        """Runs the backward plan on the stored activations; returns ``{conv name: fp32 weight gradient}``."""
+        batch, _, height, width = shape
+        plan = self.build_backward_plan(batch, height, width)
+        modules = dict(self.named_modules())
+        dev = acts["pool"].device
+        act = torch.float32 if self._precision() == 0 else self.compute_dtype
+        tensors: Dict[str, Tensor] = dict(acts)
+        keep: List[Tensor] = []
+        kinds = {"dgrad": 0, "wgrad": 1, "ingest": 2}
+        ops = []
+        for d in plan:
+            weight = scale = None
+            if d["kind"] == "ingest":
+                g = cotangents.get(d["conv"])
+                shape_nchw = (batch, d["in_channels"], d["height"], d["width"])
+                g = torch.zeros(shape_nchw, device=dev) if g is None else g.to(torch.float32).contiguous()
+                tensors[d["dz"]] = g
+                out_shape = (batch, d["height"], d["width"], d["in_channels"])
+                tensors[d["out"]] = torch.empty(out_shape, device=dev, dtype=act)
+            else:
+                conv = modules[d["conv"]]
+                bn = modules[d["conv"][:-len("conv1")] + "bn" + d["conv"][-1]] if ".downsample." not in d["conv"] \
+                    else modules[d["conv"][:-1] + "1"]
+                if d["kind"] == "wgrad":
+                    scale = self._packed_dgrad(conv, bn, False)[1]
+                    tensors[d["out"]] = torch.empty(conv.weight.shape, device=dev, dtype=torch.float32)
+                else:
+                    weight = self._packed_dgrad(conv, bn, True)[0]
+                    tensors[d["out"]] = torch.empty((batch, d["height"], d["width"], d["in_channels"]), device=dev, dtype=act)
+                keep.extend(t for t in (weight, scale) if t is not None)
+            ops.append(_hip.BackboneBwdOpStruct(
+                kinds[d["kind"]], tensors[d["dz"]].data_ptr(), _hip.ptr(tensors.get(d["x"])), _hip.ptr(weight),
+                _hip.ptr(scale), _hip.ptr(tensors.get(d["add"])), _hip.ptr(tensors.get(d["mask"])),
+                tensors[d["out"]].data_ptr(), batch, d["in_channels"], d["height"], d["width"], d["out_channels"],
+                d["kernel_size"], d["stride"], d["padding"], splits))
+        grads = {d["conv"]: tensors[d["out"]] for d in plan if d["kind"] == "wgrad"}
+        if not ops:
+            return grads
+        lib, precision = self._lib(), self._precision()
+        arr = (_hip.BackboneBwdOpStruct * len(ops))(*ops)
+        ws_bytes = lib.sdetr_backbone_bwd_workspace_bytes(arr, len(ops), precision)
+        if ws_bytes < 0:
+            _hip.check(-1, "ResNetBackbone (backward workspace)", lib)
+        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
+        _hip.check(lib.sdetr_backbone_bwd_run(_hip.stream_ptr(), arr, len(ops), precision, ws.data_ptr(), ws_bytes),
+                   "ResNetBackbone (backward run)", lib)
+        return grads
+
+
+class _ActDict(dict):
+    """A dict that can be weakly referenced (``ResNetBackbone.saved_activations``)."""
+
+
+class _BackboneTrainFunction(torch.autograd.Function):
+    """``ResNetBackbone.forward_hip_train``: inputs are the trainable conv weights, outputs the returned fp32 maps."""
+
+    @staticmethod
+    def forward(ctx, backbone: "ResNetBackbone", x: Tensor, splits: int, names: Tuple[str, ...], *weights: Tensor):
+        acts = _ActDict()
+        outputs = backbone.forward_hip(x, splits, acts)
+        ctx.backbone, ctx.acts, ctx.names, ctx.splits = backbone, acts, names, splits
+        ctx.shape = tuple(x.shape)
+        ctx.keys = sorted(outputs)
+        backbone.__dict__["_train_acts"] = weakref.ref(acts)
+        return tuple(outputs[k] for k in ctx.keys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        dws = ctx.backbone._run_backward(ctx.acts, ctx.shape, dict(zip(ctx.keys, grads)), ctx.splits)
+        return (None, None, None, None) + tuple(dws.get(n) for n in ctx.names)
 
 
 def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: bool = True,

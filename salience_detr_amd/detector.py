@@ -260,7 +260,9 @@ class SalienceDETR(SalienceDETRHead):
         without ``criterion``): float in [0, 1] or uint8, returns the detections under ``no_grad``.  Training mode:
         float32, already normalised by the dataset transforms; ``targets[i]`` = ``{"boxes": [n, 4] xyxy pixels of image
         i, "labels": [n]}``, required (``None`` raises); returns the weighted loss dict.  A detector built without
-        ``criterion`` takes the eval path under ``no_grad`` in ``train()`` mode too and ignores ``targets``.  ``noise``: the denoising generator's noise (tests)."""
+        ``criterion`` takes the eval path under ``no_grad`` in ``train()`` mode too and ignores ``targets``.  ``noise``: the denoising generator's noise (tests).
+        The backbone's backward goes through ``F.conv2d`` unless ``self.backbone.set_train_form("hip")`` was called
+        (``ResNetBackbone``: its own backward-data / backward-weight kernels)."""
         if torch.is_tensor(images):
             images = list(images.unbind(0))
         sizes = tuple((int(i.shape[-2]), int(i.shape[-1])) for i in images)
