@@ -29,11 +29,9 @@ class _AttentionQKV(Function):
         out = torch.empty_like(v)
         lse = torch.empty((B, num_heads, N), dtype=torch.float32, device=v.device)
         scale = 1.0 / math.sqrt(E // num_heads)
-        with torch.cuda.device(v.device):
-            code = _hip.lib().sdetr_attention_train_forward_f32(
-                _hip.stream_ptr(), qk.data_ptr(), N * 2 * E, 2 * E, qk.data_ptr() + 4 * E, N * 2 * E, 2 * E, v.data_ptr(), N * E, E,
-                B, num_heads, N, E // num_heads, scale, out.data_ptr(), lse.data_ptr())
-        _hip.check(code, "attention_train_forward")
+        _hip.launch("sdetr_attention_train_forward_f32", None, v.device, qk.data_ptr(), N * 2 * E, 2 * E,
+                    qk.data_ptr() + 4 * E, N * 2 * E, 2 * E, v.data_ptr(), N * E, E, B, num_heads, N, E // num_heads,
+                    scale, out.data_ptr(), lse.data_ptr(), what="attention_train_forward")
         ctx.save_for_backward(qk, v, out, lse)
         ctx.num_heads = num_heads
         return out
@@ -45,12 +43,10 @@ class _AttentionQKV(Function):
         H = ctx.num_heads
         go = grad_out.contiguous()
         gqk, gv = torch.empty_like(qk), torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            code = _hip.lib().sdetr_attention_train_backward_f32(
-                _hip.stream_ptr(), qk.data_ptr(), N * 2 * E, 2 * E, qk.data_ptr() + 4 * E, N * 2 * E, 2 * E, v.data_ptr(), N * E, E,
-                B, H, N, E // H, 1.0 / math.sqrt(E // H), out.data_ptr(), lse.data_ptr(), go.data_ptr(), gqk.data_ptr(),
-                gqk.data_ptr() + 4 * E, gv.data_ptr())
-        _hip.check(code, "attention_train_backward")
+        _hip.launch("sdetr_attention_train_backward_f32", None, v.device, qk.data_ptr(), N * 2 * E, 2 * E,
+                    qk.data_ptr() + 4 * E, N * 2 * E, 2 * E, v.data_ptr(), N * E, E, B, H, N, E // H,
+                    1.0 / math.sqrt(E // H), out.data_ptr(), lse.data_ptr(), go.data_ptr(), gqk.data_ptr(),
+                    gqk.data_ptr() + 4 * E, gv.data_ptr(), what="attention_train_backward")
         return gqk, gv, None
 
 

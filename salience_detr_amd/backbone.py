@@ -355,9 +355,8 @@ class ResNetBackbone(nn.Module):
             nbytes = lib.sdetr_backbone_packed_bytes(co, ci, k, precision)
             packed = torch.empty(nbytes // 2, dtype=torch.int16, device=f32[0].device)
             bias = torch.empty(co, dtype=torch.float32, device=f32[0].device)
-            _hip.check(lib.sdetr_backbone_pack(_hip.stream_ptr(), *[t.data_ptr() for t in f32], float(bn.eps), co, ci, k,
-                                               layout, precision, packed.data_ptr(), bias.data_ptr()),
-                       "ResNetBackbone (pack)", lib)
+            _hip.launch("sdetr_backbone_pack", lib, f32[0].device, *[t.data_ptr() for t in f32], float(bn.eps), co, ci, k,
+                        layout, precision, packed.data_ptr(), bias.data_ptr(), what="ResNetBackbone (pack)")
             return packed, bias
         return derived(conv, "backbone_packed", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build,
                        extra=(float(bn.eps), precision, self.compute_dtype, layout))
@@ -436,8 +435,8 @@ class ResNetBackbone(nn.Module):
         if ws_bytes < 0:
             _hip.check(-1, "ResNetBackbone (workspace)", lib)
         ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
-        _hip.check(lib.sdetr_backbone_run(_hip.stream_ptr(), arr, len(ops), precision, ws.data_ptr(), ws_bytes),
-                   "ResNetBackbone (run)", lib)
+        _hip.launch("sdetr_backbone_run", lib, x.device, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
+                    what="ResNetBackbone (run)")
         return outputs
 
     # ------------------------------------------------------------------------------------------ training in HIP
@@ -563,9 +562,8 @@ class ResNetBackbone(nn.Module):
                 nbytes = lib.sdetr_backbone_dgrad_packed_bytes(co, ci, k, precision)
                 packed = torch.empty(nbytes // 2, dtype=torch.int16, device=f32[0].device)
             scale = torch.empty(co, dtype=torch.float32, device=f32[0].device)
-            _hip.check(lib.sdetr_backbone_pack_dgrad(_hip.stream_ptr(), *[t.data_ptr() for t in f32], float(bn.eps), co, ci,
-                                                     k, precision, _hip.ptr(packed), scale.data_ptr()),
-                       "ResNetBackbone (pack dgrad)", lib)
+            _hip.launch("sdetr_backbone_pack_dgrad", lib, f32[0].device, *[t.data_ptr() for t in f32], float(bn.eps), co,
+                        ci, k, precision, _hip.ptr(packed), scale.data_ptr(), what="ResNetBackbone (pack dgrad)")
             return packed, scale
         return derived(conv, "backbone_packed_dgrad" if with_weight else "backbone_bn_scale",
                        (conv.weight, bn.weight, bn.running_var), build, extra=(float(bn.eps), precision, self.compute_dtype))
@@ -640,8 +638,8 @@ class ResNetBackbone(nn.Module):
         if ws_bytes < 0:
             _hip.check(-1, "ResNetBackbone (backward workspace)", lib)
         ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
-        _hip.check(lib.sdetr_backbone_bwd_run(_hip.stream_ptr(), arr, len(ops), precision, ws.data_ptr(), ws_bytes),
-                   "ResNetBackbone (backward run)", lib)
+        _hip.launch("sdetr_backbone_bwd_run", lib, dev, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
+                    what="ResNetBackbone (backward run)")
         return grads
 
 
@@ -705,10 +703,8 @@ def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: 
     mask = torch.empty(len(images), hp, wp, device=dev, dtype=torch.bool)
     ptrs = (ctypes.c_void_p * len(images))(*[im.data_ptr() for im in images])
     hw = (ctypes.c_int * (2 * len(images)))(*[int(v) for im in images for v in im.shape[1:]])
-    lib = _hip.lib()
-    _hip.check(lib.sdetr_backbone_batch_images_ex(_hip.stream_ptr(), ptrs, hw, len(images), 1 if dt == torch.uint8 else 0,
-                                                  1 if normalize else 0, hp, wp, canvas.data_ptr(), mask.data_ptr()),
-               "batch_images", lib)
+    _hip.launch("sdetr_backbone_batch_images_ex", None, dev, ptrs, hw, len(images), 1 if dt == torch.uint8 else 0,
+                1 if normalize else 0, hp, wp, canvas.data_ptr(), mask.data_ptr(), what="batch_images")
     return canvas, mask
 
 
@@ -729,8 +725,6 @@ def _resize_batch_images(images: Sequence[Tensor], size_divisible: int, resize) 
     ptrs = (ctypes.c_void_p * len(images))(*[im.data_ptr() for im in images])
     hw = (ctypes.c_int * (2 * len(images)))(*[int(v) for im in images for v in im.shape[1:]])
     out_hw = (ctypes.c_int * (2 * len(images)))(*[v for s in sizes for v in s])
-    lib = _hip.lib()
-    _hip.check(lib.sdetr_backbone_resize_batch_images(_hip.stream_ptr(), ptrs, hw, out_hw, len(images),
-                                                      1 if dt == torch.uint8 else 0, hp, wp, canvas.data_ptr(),
-                                                      mask.data_ptr()), "batch_images (resize)", lib)
+    _hip.launch("sdetr_backbone_resize_batch_images", None, dev, ptrs, hw, out_hw, len(images),
+                1 if dt == torch.uint8 else 0, hp, wp, canvas.data_ptr(), mask.data_ptr(), what="batch_images (resize)")
     return canvas, mask

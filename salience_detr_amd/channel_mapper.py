@@ -144,8 +144,8 @@ class ChannelMapper(nn.Module):
             src = w.detach().to(torch.float32).contiguous()
             nbytes = lib.sdetr_frontend_packed_bytes(src.numel(), precision)
             out = torch.empty(nbytes // 2, dtype=torch.int16, device=src.device)
-            _hip.check(lib.sdetr_frontend_pack_weight(_hip.stream_ptr(), src.data_ptr(), src.numel(), precision,
-                                                      out.data_ptr()), "ChannelMapper (pack weight)", lib)
+            _hip.launch("sdetr_frontend_pack_weight", lib, src.device, src.data_ptr(), src.numel(), precision,
+                        out.data_ptr(), what="ChannelMapper (pack weight)")
             return out
         return derived(conv, "frontend_packed_weight", (w,), build, extra=(precision, self.compute_dtype))
 
@@ -172,11 +172,10 @@ class ChannelMapper(nn.Module):
             _hip.check(-1, "ChannelMapper (workspace)", lib)
         ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=device)
         precision = self._precision()
-        s = _hip.stream_ptr()
-        _hip.check(lib.sdetr_frontend_conv(s, arr, n, batch, self.out_channels, precision, ws.data_ptr(), ws_bytes),
-                   "ChannelMapper (conv)", lib)
-        _hip.check(lib.sdetr_frontend_groupnorm(s, arr, n, batch, self.out_channels, gn.num_groups, gn.eps, ws.data_ptr(),
-                                                ws_bytes), "ChannelMapper (groupnorm)", lib)
+        _hip.launch("sdetr_frontend_conv", lib, device, arr, n, batch, self.out_channels, precision, ws.data_ptr(),
+                    ws_bytes, what="ChannelMapper (conv)")
+        _hip.launch("sdetr_frontend_groupnorm", lib, device, arr, n, batch, self.out_channels, gn.num_groups,
+                    gn.eps, ws.data_ptr(), ws_bytes, what="ChannelMapper (groupnorm)")
 
     def forward_hip(self, inputs: Sequence[Tensor]) -> List[Tensor]:
         xs = []

@@ -90,13 +90,10 @@ class _CdnQueries(torch.autograd.Function):
         mask = torch.empty((total, total), dtype=torch.bool, device=dev)
         w = weight.detach()
         lib = _hip.lib()
-        with torch.cuda.device(dev):
-            code = lib.sdetr_cdn_queries(_hip.stream_ptr(), staged.boxes.data_ptr(), staged.labels.data_ptr(),
-                                         staged.offsets.data_ptr(), staged.capacity, w.data_ptr(), _hip.ptr(noise), B,
-                                         max_gt, groups, C, E, num_queries, float(label_noise_prob),
-                                         float(box_noise_scale), label_q.data_ptr(), box_q.data_ptr(),
-                                         labels.data_ptr(), mask.data_ptr())
-        _hip.check(code, "GenerateCDNQueries", lib)
+        _hip.launch("sdetr_cdn_queries", lib, dev, staged.boxes.data_ptr(), staged.labels.data_ptr(),
+                    staged.offsets.data_ptr(), staged.capacity, w.data_ptr(), _hip.ptr(noise), B, max_gt, groups, C, E,
+                    num_queries, float(label_noise_prob), float(box_noise_scale), label_q.data_ptr(), box_q.data_ptr(),
+                    labels.data_ptr(), mask.data_ptr(), what="GenerateCDNQueries")
         ctx.save_for_backward(labels)
         ctx.num_classes = C
         ctx.mark_non_differentiable(box_q, labels, mask)
@@ -113,10 +110,8 @@ class _CdnQueries(torch.autograd.Function):
         E = g.shape[-1]
         grad_w = torch.empty((ctx.num_classes, E), dtype=torch.float32, device=g.device)
         lib = _hip.lib()
-        with torch.cuda.device(g.device):
-            code = lib.sdetr_cdn_label_grad(_hip.stream_ptr(), g.data_ptr(), labels.data_ptr(), B, n_dn,
-                                            ctx.num_classes, E, grad_w.data_ptr())
-        _hip.check(code, "GenerateCDNQueries (backward)", lib)
+        _hip.launch("sdetr_cdn_label_grad", lib, g.device, g.data_ptr(), labels.data_ptr(), B, n_dn, ctx.num_classes, E,
+                    grad_w.data_ptr(), what="GenerateCDNQueries (backward)")
         return grad_w, None, None, None, None, None, None, None
 
 

@@ -83,10 +83,8 @@ def resize_images(images: Sequence[Tensor], sizes: Sequence[Tuple[int, int]]) ->
     outs = [torch.empty(3, nh, nw, device=dev, dtype=dt) for nh, nw in sizes]
     ptrs = (ctypes.c_void_p * len(images))(*[im.data_ptr() for im in images])
     out_ptrs = (ctypes.c_void_p * len(images))(*[o.data_ptr() for o in outs])
-    lib = _hip.lib()
-    _hip.check(lib.sdetr_backbone_resize_images(_hip.stream_ptr(), ptrs, _int_pairs([im.shape[1:] for im in images]),
-                                                _int_pairs(sizes), len(images), 1 if dt == torch.uint8 else 0, out_ptrs),
-               "resize_images", lib)
+    _hip.launch("sdetr_backbone_resize_images", None, dev, ptrs, _int_pairs([im.shape[1:] for im in images]),
+                _int_pairs(sizes), len(images), 1 if dt == torch.uint8 else 0, out_ptrs, what="resize_images")
     return outs
 
 

@@ -67,21 +67,19 @@ def masked_topk_desc(score: Tensor, k: int, mask: Optional[Tensor] = None, fill_
     else:
         out_score = torch.empty((B, k), dtype=torch.float32, device=score.device) if want_scores else None
         out_index = torch.empty((B, k), dtype=torch.int64, device=score.device)
-    lib = _hip.lib()
-    ws_bytes = lib.sdetr_topk_workspace_bytes(B, N, k)
+    ws_bytes = _hip.lib().sdetr_topk_workspace_bytes(B, N, k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=score.device) if ws_bytes else None
-    args = (_hip.stream_ptr(), score.data_ptr(), _hip.ptr(mask), mask_stride,
+    args = (score.data_ptr(), _hip.ptr(mask), mask_stride,
             (2 if fill_value is not None else 1) if fill_with_global_min else 0, _hip.ptr(fill_value),
             _hip.ptr(payload), B, N, k, int(index_offset), _hip.ptr(out_score), out_index.data_ptr(), out_stride,
             _hip.ptr(ws), ws_bytes)
-    with torch.cuda.device(score.device):
-        if orders_job is not None and not orders_job.done and orders_job.device == score.device:
-            # the encoder's row orders ride in this launch (or run right behind it when it is not the one-launch sort)
-            code = lib.sdetr_masked_topk_desc_with_orders_f32(*args, ctypes.byref(orders_job.struct))
-            orders_job.done = True
-        else:
-            code = lib.sdetr_masked_topk_desc_f32(*args)
-    _hip.check(code, "masked_topk_desc")
+    if orders_job is not None and not orders_job.done and orders_job.device == score.device:
+        # the encoder's row orders ride in this launch (or run right behind it when it is not the one-launch sort)
+        _hip.launch("sdetr_masked_topk_desc_with_orders_f32", None, score.device, *args, ctypes.byref(orders_job.struct),
+                    what="masked_topk_desc")
+        orders_job.done = True
+    else:
+        _hip.launch("sdetr_masked_topk_desc_f32", None, score.device, *args, what="masked_topk_desc")
     return out_score, out_index
 
 
@@ -158,22 +156,19 @@ def _sorted_slices_topk(score: Tensor, k: int, mask: Optional[Tensor], fill_valu
         out_score = torch.empty((B, k), dtype=torch.float32, device=score.device) if want_scores else None
         out_index = torch.empty((B, k), dtype=torch.int64, device=score.device)
         out_stride = k
-    lib = _hip.lib()
-    ws_bytes = lib.sdetr_topk_sliced_workspace_bytes(B, N)
+    ws_bytes = _hip.lib().sdetr_topk_sliced_workspace_bytes(B, N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=score.device)
     job = carry_rank if carry_rank is not None and not carry_rank.done and carry_rank.score.device == score.device else None
     fin = (carry_finalize if carry_finalize is not None and not carry_finalize.done
            and carry_finalize.tokens.device == score.device else None)
-    if fin is not None:
-        lib = _hip.lib(fin.tokens.dtype)      # (the pass works on 16-bit activations: it picks the library)
+    act = fin.tokens.dtype if fin is not None else None      # (the pass works on 16-bit activations: it picks the library)
     carried = ctypes.c_int(0)
-    with torch.cuda.device(score.device):
-        code = lib.sdetr_masked_topk_sliced_with_rank_f32(
-            _hip.stream_ptr(), score.data_ptr(), _hip.ptr(mask), mask_stride, _hip.ptr(fill_value) if mask is not None else None,
-            B, N, k, _MERGE_SEGMENTS, int(index_offset), _hip.ptr(out_score), out_index.data_ptr(), out_stride,
-            ws.data_ptr(), ws_bytes, ctypes.byref(job.struct()) if job is not None else None,
-            ctypes.byref(fin.struct()) if fin is not None else None, ctypes.byref(carried))
-    _hip.check(code, "masked_topk_desc (sliced)")
+    _hip.launch("sdetr_masked_topk_sliced_with_rank_f32", act, score.device, score.data_ptr(), _hip.ptr(mask),
+                mask_stride, _hip.ptr(fill_value) if mask is not None else None, B, N, k, _MERGE_SEGMENTS,
+                int(index_offset), _hip.ptr(out_score), out_index.data_ptr(), out_stride, ws.data_ptr(), ws_bytes,
+                ctypes.byref(job.struct()) if job is not None else None,
+                ctypes.byref(fin.struct()) if fin is not None else None, ctypes.byref(carried),
+                what="masked_topk_desc (sliced)")
     if carried.value:
         if job is not None:
             job.done = True
@@ -255,10 +250,8 @@ def gather_rows(src: Tensor, idx: Tensor) -> Tensor:
     dst = torch.empty((B, n) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
     if B * n == 0:
         return dst
-    with torch.cuda.device(src.device):
-        code = _hip.lib().sdetr_gather_rows(_hip.stream_ptr(), src.data_ptr(), idx.data_ptr(), B, S, n, row_bytes,
-                                            dst.data_ptr())
-    _hip.check(code, "gather_rows")
+    _hip.launch("sdetr_gather_rows", None, src.device, src.data_ptr(), idx.data_ptr(), B, S, n, row_bytes,
+                dst.data_ptr())
     return dst
 
 
@@ -275,10 +268,8 @@ def scatter_rows_(dst: Tensor, idx: Tensor, src: Tensor, count: Optional[Tensor]
     if B * n == 0:
         return dst
     row_bytes = dst[0, 0].numel() * dst.element_size()
-    with torch.cuda.device(dst.device):
-        code = _hip.lib().sdetr_scatter_rows(_hip.stream_ptr(), dst.data_ptr(), idx.data_ptr(), src.data_ptr(),
-                                             _hip.ptr(count), B, S, n, row_bytes)
-    _hip.check(code, "scatter_rows_")
+    _hip.launch("sdetr_scatter_rows", None, dst.device, dst.data_ptr(), idx.data_ptr(), src.data_ptr(), _hip.ptr(count),
+                B, S, n, row_bytes, what="scatter_rows_")
     return dst
 
 
@@ -317,30 +308,25 @@ def pyramid_flatten(multi_level_feats, multi_level_pos_embeds, multi_level_masks
     pos_bf16 = torch.empty((B, S, C), dtype=act, device=dev) if want_bf16 else None
     le = level_embeds.detach().float().contiguous()
     valid_ratios = torch.empty((B, len(feats), 2), dtype=torch.float32, device=dev)
-    lib = _hip.lib(act)
     start = 0
     L = len(feats)
     if (flatten_one_launch if one_launch is None else one_launch) and L <= 8:
         mu8s = [m.view(torch.uint8) if m.dtype == torch.bool else m for m in masks]
         ptrs = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
         ints = lambda vs: (ctypes.c_int * L)(*vs)
-        with torch.cuda.device(dev):
-            code = lib.sdetr_pyramid_flatten(
-                _hip.stream_ptr(), L, ptrs(feats), ptrs(pos), ptrs(mu8s), ints([int(f.shape[2]) for f in feats]),
-                ints([int(f.shape[3]) for f in feats]), le.data_ptr(), B, C, S, _hip.ptr(feat_out), _hip.ptr(pos_out),
-                sum_out.data_ptr(), mask_out.data_ptr(), _hip.ptr(feat_bf16), _hip.ptr(pos_bf16), valid_ratios.data_ptr())
-        _hip.check(code, "pyramid_flatten")
+        _hip.launch("sdetr_pyramid_flatten", act, dev, L, ptrs(feats), ptrs(pos), ptrs(mu8s),
+                    ints([int(f.shape[2]) for f in feats]), ints([int(f.shape[3]) for f in feats]), le.data_ptr(), B, C,
+                    S, _hip.ptr(feat_out), _hip.ptr(pos_out), sum_out.data_ptr(), mask_out.data_ptr(),
+                    _hip.ptr(feat_bf16), _hip.ptr(pos_bf16), valid_ratios.data_ptr())
         return feat_out, pos_out, sum_out, mask_out, feat_bf16, pos_bf16, valid_ratios
-    with torch.cuda.device(dev):
-        for lvl, (f, p, m) in enumerate(zip(feats, pos, masks)):
-            H, W = int(f.shape[2]), int(f.shape[3])
-            mu8 = m.view(torch.uint8) if m.dtype == torch.bool else m
-            code = lib.sdetr_pyramid_flatten_level(
-                _hip.stream_ptr(), f.data_ptr(), p.data_ptr(), mu8.data_ptr(), le[lvl].data_ptr(), B, C, H, W, lvl,
-                start, S, _hip.ptr(feat_out), _hip.ptr(pos_out), sum_out.data_ptr(), mask_out.data_ptr(),
-                _hip.ptr(feat_bf16), _hip.ptr(pos_bf16), valid_ratios.data_ptr() + lvl * 8, len(feats) * 2)
-            _hip.check(code, "pyramid_flatten_level")
-            start += H * W
+    for lvl, (f, p, m) in enumerate(zip(feats, pos, masks)):
+        H, W = int(f.shape[2]), int(f.shape[3])
+        mu8 = m.view(torch.uint8) if m.dtype == torch.bool else m
+        _hip.launch("sdetr_pyramid_flatten_level", act, dev, f.data_ptr(), p.data_ptr(), mu8.data_ptr(), le[lvl].data_ptr(),
+                    B, C, H, W, lvl, start, S, _hip.ptr(feat_out), _hip.ptr(pos_out), sum_out.data_ptr(),
+                    mask_out.data_ptr(), _hip.ptr(feat_bf16), _hip.ptr(pos_bf16), valid_ratios.data_ptr() + lvl * 8,
+                    len(feats) * 2)
+        start += H * W
     return feat_out, pos_out, sum_out, mask_out, feat_bf16, pos_bf16, valid_ratios
 
 
@@ -355,11 +341,8 @@ def class_max_times(score: Tensor, scale: Tensor) -> Tensor:
     if scale.dtype != torch.float32 or scale.dim() != 2 or (Nq > 1 and scale.stride(1) != 1):
         scale = scale.float().contiguous()
     out = torch.empty((B, Nq), dtype=torch.float32, device=score.device)
-    with torch.cuda.device(score.device):
-        code = _hip.lib(score.dtype).sdetr_class_max_times(_hip.stream_ptr(), score.data_ptr(), _hip.dtype_code(score.dtype),
-                                                scale.data_ptr(), scale.stride(0) if B > 1 else max(Nq, 1), B, Nq, C,
-                                                out.data_ptr())
-    _hip.check(code, "class_max_times")
+    _hip.launch("sdetr_class_max_times", score.dtype, score.device, score.data_ptr(), _hip.dtype_code(score.dtype),
+                scale.data_ptr(), scale.stride(0) if B > 1 else max(Nq, 1), B, Nq, C, out.data_ptr())
     return out
 
 
@@ -413,13 +396,11 @@ def fused_layer_norm(x: Tensor, norm: torch.nn.LayerNorm, residual: Optional[Ten
     else:
         out_dtype = out_dtype or x.dtype
         out = torch.empty((B, n, C), dtype=out_dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype if _hip.is_act16(x.dtype) else out_dtype).sdetr_layernorm(
-            _hip.stream_ptr(), xv.data_ptr(), _hip.ptr(rv), _hip.dtype_code(x.dtype), xbs, xrs, rbs, rrs,
-            _hip.ptr(row_scale), _hip.ptr(alpha), w.data_ptr(), b.data_ptr(), _hip.dtype_code(w.dtype),
-            float(norm.eps), B, n, C, out.data_ptr(), _hip.dtype_code(out_dtype), _hip.ptr(scatter_index), out_rows,
-            1 if gather_x else 0)
-    _hip.check(code, "fused_layer_norm")
+    _hip.launch("sdetr_layernorm", x.dtype if _hip.is_act16(x.dtype) else out_dtype, x.device, xv.data_ptr(),
+                _hip.ptr(rv), _hip.dtype_code(x.dtype), xbs, xrs, rbs, rrs, _hip.ptr(row_scale), _hip.ptr(alpha),
+                w.data_ptr(), b.data_ptr(), _hip.dtype_code(w.dtype), float(norm.eps), B, n, C, out.data_ptr(),
+                _hip.dtype_code(out_dtype), _hip.ptr(scatter_index), out_rows, 1 if gather_x else 0,
+                what="fused_layer_norm")
     return out if scatter_index is not None else out.view(shape)
 
 
@@ -431,10 +412,8 @@ def column_mean(x: Tensor) -> Tensor:
         raise RuntimeError("column_mean: fp32 [B,n,C] with a contiguous last dim expected")
     B, n, C = x.shape
     out = torch.empty((B, 1, C), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        code = _hip.lib().sdetr_column_mean_f32(_hip.stream_ptr(), x.data_ptr(), x.stride(0), x.stride(1), B, n, C,
-                                                out.data_ptr())
-    _hip.check(code, "column_mean")
+    _hip.launch("sdetr_column_mean_f32", None, x.device, x.data_ptr(), x.stride(0), x.stride(1), B, n, C,
+                out.data_ptr(), what="column_mean")
     return out
 
 
@@ -461,16 +440,10 @@ def packed_linear_weight(weight: Tensor, cols=None, split3: bool = False) -> Ten
         w = w[:, cols[0]:cols[1]]
 
     def build():
-        with torch.cuda.device(w.device):
-            if split3:
-                out = torch.empty(w.shape[0] * w.shape[1] * 3, dtype=torch.bfloat16, device=w.device)
-                code = _hip.lib().sdetr_pack_linear_bf16x3(_hip.stream_ptr(), w.data_ptr(), w.stride(0), w.shape[0],
-                                                           w.shape[1], out.data_ptr())
-            else:
-                out = torch.empty(w.shape[0] * w.shape[1], dtype=torch.float32, device=w.device)
-                code = _hip.lib().sdetr_pack_linear_f32(_hip.stream_ptr(), w.data_ptr(), w.stride(0), w.shape[0],
-                                                        w.shape[1], out.data_ptr())
-        _hip.check(code, "pack_linear")
+        out = torch.empty(w.shape[0] * w.shape[1] * (3 if split3 else 1), dtype=torch.bfloat16 if split3 else torch.float32,
+                          device=w.device)
+        _hip.launch("sdetr_pack_linear_bf16x3" if split3 else "sdetr_pack_linear_f32", None, w.device, w.data_ptr(),
+                    w.stride(0), w.shape[0], w.shape[1], out.data_ptr(), what="pack_linear")
         return out
     return derived(weight, "packed_linear_x3" if split3 else "packed_linear", (weight,), build, extra=cols)
 
@@ -500,10 +473,8 @@ class ValueProjectionJob:
         if self.done:
             return
         x, pw, b, pad, B, Nv, heads, groups, dst, code_, lay = self.pointers()
-        with torch.cuda.device(self.value.device):
-            code = _hip.lib(self.value.dtype).sdetr_value_proj_head_major(_hip.stream_ptr(), x, pw, b, pad, B, Nv, 256, heads, 32, groups,
-                                                          dst, code_, lay)
-        _hip.check(code, "value_proj_head_major")
+        _hip.launch("sdetr_value_proj_head_major", self.value.dtype, self.value.device, x, pw, b, pad, B, Nv, 256,
+                    heads, 32, groups, dst, code_, lay)
         self.done = True
 
 
@@ -612,13 +583,10 @@ def salience_head_hoist(x: Tensor, predictor, enc_output=None, enc_output_norm=N
                  and finalize_job.tokens.device == x.device)
     vp = value_job.pointers() if carry_value else (None, None, None, None, 0, 0, 0, 0, None, 0, None)
     fj = ctypes.byref(finalize_job.struct()) if carry_fin else None
-    with torch.cuda.device(x.device):
-        code = lib.sdetr_salience_head_hoist_x3(
-            _hip.stream_ptr(), x.data_ptr(), x.stride(0), x.stride(1), B, S, C, _hip.ptr(w_enc), _hip.ptr(b_enc),
-            _hip.ptr(g_enc), _hip.ptr(be_enc), eps_enc, l1n.weight.data_ptr(),
-            packed_linear_weight(l1.weight, split3=True).data_ptr(), _hip.ptr(memory_out), mbs, g.data_ptr(), g.stride(0),
-            sigma.data_ptr(), sigma.stride(0), *vp, fj)
-    _hip.check(code, "salience_head_hoist")
+    _hip.launch("sdetr_salience_head_hoist_x3", lib, x.device, x.data_ptr(), x.stride(0), x.stride(1), B, S, C,
+                _hip.ptr(w_enc), _hip.ptr(b_enc), _hip.ptr(g_enc), _hip.ptr(be_enc), eps_enc, l1n.weight.data_ptr(),
+                packed_linear_weight(l1.weight, split3=True).data_ptr(), _hip.ptr(memory_out), mbs, g.data_ptr(),
+                g.stride(0), sigma.data_ptr(), sigma.stride(0), *vp, fj, what="salience_head_hoist")
     if carry_value:
         value_job.done = True
     if carry_fin:
@@ -692,16 +660,14 @@ def salience_head_hoist_pyramid(multi_level_feats, multi_level_pos_embeds, multi
     ptrs = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
     ints = lambda vs: (ctypes.c_int * L)(*vs)
     lib = _hip.lib(act)
-    with torch.cuda.device(dev):
-        code = lib.sdetr_salience_head_hoist_pyramid_x3(
-            _hip.stream_ptr(), L, ptrs(feats), ptrs(pos), ptrs(mu8s), ints([int(f.shape[2]) for f in feats]),
-            ints([int(f.shape[3]) for f in feats]), le.data_ptr(), B, C, S, mask_out.data_ptr(), feat_act.data_ptr(),
-            pos_act.data_ptr(), valid_ratios.data_ptr(), packed_linear_weight(enc_output.weight, split3=True).data_ptr(),
-            enc_output.bias.detach().data_ptr(), enc_output_norm.weight.detach().data_ptr(),
-            enc_output_norm.bias.detach().data_ptr(), float(enc_output_norm.eps), l1n.weight.data_ptr(),
-            packed_linear_weight(l1.weight, split3=True).data_ptr(), _hip.ptr(memory_out), mbs, g.data_ptr(), g.stride(0),
-            sigma.data_ptr(), sigma.stride(0))
-    _hip.check(code, "salience_head_hoist_pyramid")
+    _hip.launch("sdetr_salience_head_hoist_pyramid_x3", lib, dev, L, ptrs(feats), ptrs(pos), ptrs(mu8s),
+                ints([int(f.shape[2]) for f in feats]), ints([int(f.shape[3]) for f in feats]), le.data_ptr(), B, C, S,
+                mask_out.data_ptr(), feat_act.data_ptr(), pos_act.data_ptr(), valid_ratios.data_ptr(),
+                packed_linear_weight(enc_output.weight, split3=True).data_ptr(), enc_output.bias.detach().data_ptr(),
+                enc_output_norm.weight.detach().data_ptr(), enc_output_norm.bias.detach().data_ptr(),
+                float(enc_output_norm.eps), l1n.weight.data_ptr(),
+                packed_linear_weight(l1.weight, split3=True).data_ptr(), _hip.ptr(memory_out), mbs, g.data_ptr(),
+                g.stride(0), sigma.data_ptr(), sigma.stride(0), what="salience_head_hoist_pyramid")
     return HoistedHead(g, sigma, c0), mask_out, feat_act, pos_act, valid_ratios
 
 
@@ -772,72 +738,62 @@ def salience_head(x: Tensor, predictor, row_scale: Optional[Tensor] = None, coar
         if score_flat.shape != score.shape or score_flat.stride(1) != 1 or score_flat.dtype != torch.float32:
             raise RuntimeError("salience_head: score_flat must be a fp32 [B,n] slice with a contiguous last dim")
         sfs = score_flat.stride(0)
-    with torch.cuda.device(x.device):
-        s = _hip.stream_ptr()
-        stage1_args = (
-            s, x.data_ptr(), x.stride(0), x.stride(1), B, n, C, _hip.ptr(w_enc), _hip.ptr(b_enc), _hip.ptr(g_enc),
-            _hip.ptr(be_enc), eps_enc, _hip.ptr(row_scale), _hip.ptr(coarse_score), ch, cw, lh, lw, _hip.ptr(alpha),
-            l1n.weight.data_ptr(), l1n.bias.data_ptr(), float(l1n.eps),
-            packed_linear_weight(l1.weight, split3=x3).data_ptr(),
-            l1.bias.data_ptr(), _hip.ptr(memory_out), mbs, z_local.data_ptr(), partial.data_ptr())
-        # a coarse level of the hoisted head takes stage 2's per-image constant in stage 2's own blocks (no const launch)
-        const_in_block = hoisted is not None and x3 and CONST_IN_BLOCK and nblk <= CONST_IN_BLOCK_ROWS
-        if hoisted is not None:
-            if hoisted.g.shape != x.shape or hoisted.g.stride(2) != 1 or hoisted.g.stride(1) != C or hoisted.sigma.stride(1) != 1:
-                raise RuntimeError("salience_head: hoisted rows must be [B,n,256] / [B,n] slices with contiguous rows")
-            value_job = None
-        carry_value = x3 and value_job is not None and not value_job.done and value_job.value.device == x.device
-        carry_rank = x3 and rank_job is not None and not rank_job.done and rank_job.score.device == x.device
-        carry_fin = (x3 and finalize_job is not None and not finalize_job.done and not carry_value
-                     and finalize_job.tokens.device == x.device)
-        if hoisted is not None:
-            rk = ctypes.byref(rank_job.struct()) if carry_rank else None
-            fj = ctypes.byref(finalize_job.struct()) if carry_fin else None
-            code = lib.sdetr_salience_head_modulate(
-                s, hoisted.g.data_ptr(), hoisted.g.stride(0), hoisted.sigma.data_ptr(), hoisted.sigma.stride(0), B, n,
-                _hip.ptr(row_scale), _hip.ptr(coarse_score), ch, cw, lh, lw, _hip.ptr(alpha), float(l1n.eps),
-                hoisted.c0.data_ptr(), z_local.data_ptr(), partial.data_ptr(), rk, fj,
-                _hip.ptr(score_min) if const_in_block else None)
-            if carry_rank:
-                rank_job.done = True
-            if carry_fin:
-                finalize_job.done = True
-        elif carry_value or carry_rank or carry_fin:
-            vp = value_job.pointers() if carry_value else (None, None, None, None, 0, 0, 0, 0, None, 0, None)
-            rk = ctypes.byref(rank_job.struct()) if carry_rank else None
-            fj = ctypes.byref(finalize_job.struct()) if carry_fin else None
-            code = lib.sdetr_stage1_x3_with_jobs(*stage1_args, *vp, rk, fj)
-            if carry_value:
-                value_job.done = True
-            if carry_rank:
-                rank_job.done = True
-            if carry_fin:
-                finalize_job.done = True
-        else:
-            stage1 = lib.sdetr_salience_head_stage1_x3 if x3 else lib.sdetr_salience_head_stage1
-            code = stage1(*stage1_args)
-        _hip.check(code, "salience_head_stage1")
-        # (with the bf16x3 kernels stage 2's first product takes the three-plane packing too: no f32 MFMA in front of GELU)
-        w2_local = None if x3 else packed_linear_weight(l2a.weight, cols=(0, half)).data_ptr()
-        w2_x3 = packed_linear_weight(l2a.weight, cols=(0, half), split3=True).data_ptr() if x3 else None
-        w3 = packed_linear_weight(l2b.weight).data_ptr()
-        if value_job2 is not None and not value_job2.done and value_job2.value.device == x.device:
-            if not const_in_block:
-                code = lib.sdetr_salience_head_const(s, partial.data_ptr(), B, n, l2a.weight.data_ptr(), l2a.bias.data_ptr(),
-                                                     cst.data_ptr(), _hip.ptr(score_min))
-                _hip.check(code, "salience_head_const")
-            code = lib.sdetr_stage2_with_value_proj(
-                s, z_local.data_ptr(), B, n, w2_local, w3, l2b.bias.data_ptr(), l2c.weight.data_ptr(),
-                l2c.bias.data_ptr(), cst.data_ptr(), score.data_ptr(), _hip.ptr(score_flat), sfs, _hip.ptr(score_min),
-                *value_job2.pointers(), w2_x3, partial.data_ptr() if const_in_block else None,
-                l2a.weight.data_ptr() if const_in_block else None, l2a.bias.data_ptr() if const_in_block else None)
-            value_job2.done = True
-        else:
-            code = lib.sdetr_salience_head_stage2(
-                s, z_local.data_ptr(), partial.data_ptr(), B, n, l2a.weight.data_ptr(), l2a.bias.data_ptr(),
-                w2_local, w3, l2b.bias.data_ptr(), l2c.weight.data_ptr(), l2c.bias.data_ptr(), cst.data_ptr(),
-                score.data_ptr(), _hip.ptr(score_flat), sfs, _hip.ptr(score_min), w2_x3, 1 if const_in_block else 0)
-        _hip.check(code, "salience_head_stage2")
+    dev = x.device
+    stage1_args = (
+        x.data_ptr(), x.stride(0), x.stride(1), B, n, C, _hip.ptr(w_enc), _hip.ptr(b_enc), _hip.ptr(g_enc),
+        _hip.ptr(be_enc), eps_enc, _hip.ptr(row_scale), _hip.ptr(coarse_score), ch, cw, lh, lw, _hip.ptr(alpha),
+        l1n.weight.data_ptr(), l1n.bias.data_ptr(), float(l1n.eps),
+        packed_linear_weight(l1.weight, split3=x3).data_ptr(),
+        l1.bias.data_ptr(), _hip.ptr(memory_out), mbs, z_local.data_ptr(), partial.data_ptr())
+    # a coarse level of the hoisted head takes stage 2's per-image constant in stage 2's own blocks (no const launch)
+    const_in_block = hoisted is not None and x3 and CONST_IN_BLOCK and nblk <= CONST_IN_BLOCK_ROWS
+    if hoisted is not None:
+        if hoisted.g.shape != x.shape or hoisted.g.stride(2) != 1 or hoisted.g.stride(1) != C or hoisted.sigma.stride(1) != 1:
+            raise RuntimeError("salience_head: hoisted rows must be [B,n,256] / [B,n] slices with contiguous rows")
+        value_job = None
+    carry_value = x3 and value_job is not None and not value_job.done and value_job.value.device == dev
+    carry_rank = x3 and rank_job is not None and not rank_job.done and rank_job.score.device == dev
+    carry_fin = (x3 and finalize_job is not None and not finalize_job.done and not carry_value
+                 and finalize_job.tokens.device == dev)
+    rk = ctypes.byref(rank_job.struct()) if carry_rank else None
+    fj = ctypes.byref(finalize_job.struct()) if carry_fin else None
+    if hoisted is not None:
+        _hip.launch("sdetr_salience_head_modulate", lib, dev, hoisted.g.data_ptr(), hoisted.g.stride(0),
+                    hoisted.sigma.data_ptr(), hoisted.sigma.stride(0), B, n, _hip.ptr(row_scale), _hip.ptr(coarse_score),
+                    ch, cw, lh, lw, _hip.ptr(alpha), float(l1n.eps), hoisted.c0.data_ptr(), z_local.data_ptr(),
+                    partial.data_ptr(), rk, fj, _hip.ptr(score_min) if const_in_block else None,
+                    what="salience_head_stage1")
+    elif carry_value or carry_rank or carry_fin:
+        vp = value_job.pointers() if carry_value else (None, None, None, None, 0, 0, 0, 0, None, 0, None)
+        _hip.launch("sdetr_stage1_x3_with_jobs", lib, dev, *stage1_args, *vp, rk, fj, what="salience_head_stage1")
+    else:
+        _hip.launch("sdetr_salience_head_stage1_x3" if x3 else "sdetr_salience_head_stage1", lib, dev, *stage1_args,
+                    what="salience_head_stage1")
+    if carry_value:
+        value_job.done = True
+    if carry_rank:
+        rank_job.done = True
+    if carry_fin:
+        finalize_job.done = True
+    # (with the bf16x3 kernels stage 2's first product takes the three-plane packing too: no f32 MFMA in front of GELU)
+    w2_local = None if x3 else packed_linear_weight(l2a.weight, cols=(0, half)).data_ptr()
+    w2_x3 = packed_linear_weight(l2a.weight, cols=(0, half), split3=True).data_ptr() if x3 else None
+    w3 = packed_linear_weight(l2b.weight).data_ptr()
+    if value_job2 is not None and not value_job2.done and value_job2.value.device == dev:
+        if not const_in_block:
+            _hip.launch("sdetr_salience_head_const", lib, dev, partial.data_ptr(), B, n, l2a.weight.data_ptr(),
+                        l2a.bias.data_ptr(), cst.data_ptr(), _hip.ptr(score_min))
+        _hip.launch("sdetr_stage2_with_value_proj", lib, dev, z_local.data_ptr(), B, n, w2_local, w3, l2b.bias.data_ptr(),
+                    l2c.weight.data_ptr(), l2c.bias.data_ptr(), cst.data_ptr(), score.data_ptr(), _hip.ptr(score_flat), sfs,
+                    _hip.ptr(score_min), *value_job2.pointers(), w2_x3, partial.data_ptr() if const_in_block else None,
+                    l2a.weight.data_ptr() if const_in_block else None, l2a.bias.data_ptr() if const_in_block else None,
+                    what="salience_head_stage2")
+        value_job2.done = True
+    else:
+        _hip.launch("sdetr_salience_head_stage2", lib, dev, z_local.data_ptr(), partial.data_ptr(), B, n,
+                    l2a.weight.data_ptr(), l2a.bias.data_ptr(), w2_local, w3, l2b.bias.data_ptr(), l2c.weight.data_ptr(),
+                    l2c.bias.data_ptr(), cst.data_ptr(), score.data_ptr(), _hip.ptr(score_flat), sfs, _hip.ptr(score_min),
+                    w2_x3, 1 if const_in_block else 0)
     return score
 
 
@@ -855,12 +811,9 @@ def advance_rows(layer_out: Tensor, sorted_result: Tensor, next_rows: int, token
     if count is not None and (count.dtype != torch.int64 or count.numel() != B):
         raise RuntimeError("advance_rows: count must be int64 [B]")
     nxt = torch.empty((B, next_rows, C), dtype=layer_out.dtype, device=layer_out.device) if next_rows > 0 else None
-    with torch.cuda.device(layer_out.device):
-        code = _hip.lib(layer_out.dtype).sdetr_advance_rows(
-            _hip.stream_ptr(), layer_out.data_ptr(), sorted_result.data_ptr(), _hip.ptr(nxt), tokens.data_ptr(),
-            sorted_index.data_ptr(), sorted_index.stride(0), _hip.ptr(count), B, rows, sorted_result.shape[1],
-            int(next_rows), tokens.shape[1], C * layer_out.element_size())
-    _hip.check(code, "advance_rows")
+    _hip.launch("sdetr_advance_rows", layer_out.dtype, layer_out.device, layer_out.data_ptr(), sorted_result.data_ptr(),
+                _hip.ptr(nxt), tokens.data_ptr(), sorted_index.data_ptr(), sorted_index.stride(0), _hip.ptr(count), B,
+                rows, sorted_result.shape[1], int(next_rows), tokens.shape[1], C * layer_out.element_size())
     return nxt
 
 
@@ -880,11 +833,9 @@ def select_stack(query: Tensor, pos: Tensor, index: Tensor) -> Tensor:
     B, _, C = query.shape
     N = index.shape[1]
     out = torch.empty((B, 2 * N, C), dtype=query.dtype, device=query.device)
-    with torch.cuda.device(query.device):
-        code = _hip.lib(query.dtype).sdetr_select_stack(
-            _hip.stream_ptr(), query.data_ptr(), _batch_stride(query, "select_stack"), pos.data_ptr(),
-            _batch_stride(pos, "select_stack"), index.data_ptr(), B, N, C, _hip.dtype_code(query.dtype), out.data_ptr())
-    _hip.check(code, "select_stack")
+    _hip.launch("sdetr_select_stack", query.dtype, query.device, query.data_ptr(), _batch_stride(query, "select_stack"),
+                pos.data_ptr(), _batch_stride(pos, "select_stack"), index.data_ptr(), B, N, C,
+                _hip.dtype_code(query.dtype), out.data_ptr())
     return out
 
 
@@ -936,20 +887,15 @@ def encoder_finalize(tokens: Tensor, sorted_result: Tensor, sorted_index: Tensor
                                              else padding_mask)
     if finalize_job is not None and finalize_job.done and finalize_job.tokens is tokens:
         out = finalize_job.out      # the token-space pass has run (carried by a filtering launch): sorted rows only
-        with torch.cuda.device(tokens.device):
-            code = _hip.lib(tokens.dtype).sdetr_encoder_finalize_sorted(
-                _hip.stream_ptr(), tokens.data_ptr(), sorted_result.data_ptr(), sorted_index.data_ptr(), _hip.ptr(count),
-                background.data_ptr(), _hip.ptr(pad), B, S, sorted_result.shape[1], int(last_rows), C,
-                _hip.dtype_code(tokens.dtype), out.data_ptr())
-        _hip.check(code, "encoder_finalize")
+        _hip.launch("sdetr_encoder_finalize_sorted", tokens.dtype, tokens.device, tokens.data_ptr(),
+                    sorted_result.data_ptr(), sorted_index.data_ptr(), _hip.ptr(count), background.data_ptr(),
+                    _hip.ptr(pad), B, S, sorted_result.shape[1], int(last_rows), C, _hip.dtype_code(tokens.dtype),
+                    out.data_ptr(), what="encoder_finalize")
         return out
     out = torch.empty_like(tokens)
-    with torch.cuda.device(tokens.device):
-        code = _hip.lib(tokens.dtype).sdetr_encoder_finalize(
-            _hip.stream_ptr(), tokens.data_ptr(), sorted_result.data_ptr(), sorted_index.data_ptr(), _hip.ptr(count),
-            background.data_ptr(), _hip.ptr(pad), B, S, sorted_result.shape[1], int(last_rows), C,
-            _hip.dtype_code(tokens.dtype), out.data_ptr())
-    _hip.check(code, "encoder_finalize")
+    _hip.launch("sdetr_encoder_finalize", tokens.dtype, tokens.device, tokens.data_ptr(), sorted_result.data_ptr(),
+                sorted_index.data_ptr(), _hip.ptr(count), background.data_ptr(), _hip.ptr(pad), B, S,
+                sorted_result.shape[1], int(last_rows), C, _hip.dtype_code(tokens.dtype), out.data_ptr())
     return out
 
 
@@ -975,8 +921,8 @@ def _ffn_operands(linear1, linear2, norm):
         with torch.no_grad(), torch.cuda.device(dev):
             packed = torch.empty(lib.sdetr_ffn_packed_bytes(F), dtype=torch.uint8, device=dev)
             w1, w2 = linear1.weight.detach().contiguous(), linear2.weight.detach().contiguous()
-            code = lib.sdetr_ffn_pack_bf16(_hip.stream_ptr(), w1.data_ptr(), w2.data_ptr(), 256, F, packed.data_ptr())
-            _hip.check(code, "ffn_pack")
+            _hip.launch("sdetr_ffn_pack_bf16", lib, dev, w1.data_ptr(), w2.data_ptr(), 256, F, packed.data_ptr(),
+                        what="ffn_pack")
             small = [t.detach().float().contiguous() for t in (linear1.bias, linear2.bias, norm.weight, norm.bias)]
         return packed, small
     return derived(linear1.weight, "ffn", (linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm.weight,
@@ -998,14 +944,13 @@ def fused_ffn(x: Tensor, linear1, linear2, norm, hidden_splits: Optional[int] = 
         x2 = x2.contiguous()
     out = torch.empty_like(x2)
     T = x2.shape[0]
-    with torch.cuda.device(x.device):
+    with torch.cuda.device(x.device):      # (the choice reads the current device's CU count)
         splits = int(hidden_splits) if hidden_splits else lib.sdetr_ffn_auto_splits(T, F)
-        ws_bytes = lib.sdetr_ffn_workspace_bytes(T, splits)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-        code = lib.sdetr_ffn_fused_bf16(_hip.stream_ptr(), x2.data_ptr(), packed.data_ptr(), b1.data_ptr(),
-                                        b2.data_ptr(), g.data_ptr(), be.data_ptr(), float(norm.eps), T, 256, F,
-                                        out.data_ptr(), splits, _hip.ptr(ws), ws_bytes)
-    _hip.check(code, "ffn_fused")
+    ws_bytes = lib.sdetr_ffn_workspace_bytes(T, splits)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    _hip.launch("sdetr_ffn_fused_bf16", lib, x.device, x2.data_ptr(), packed.data_ptr(), b1.data_ptr(), b2.data_ptr(),
+                g.data_ptr(), be.data_ptr(), float(norm.eps), T, 256, F, out.data_ptr(), splits, _hip.ptr(ws), ws_bytes,
+                what="ffn_fused")
     return out.view(x.shape)
 
 
@@ -1030,16 +975,15 @@ def fused_ffn_advance(x: Tensor, linear1, linear2, norm, sorted_result: Tensor, 
     F = linear1.out_features
     packed, (b1, b2, g, be) = _ffn_operands(linear1, linear2, norm)
     nxt = torch.empty((B, next_rows, C), dtype=x.dtype, device=x.device) if next_rows > 0 else None
-    with torch.cuda.device(x.device):
+    with torch.cuda.device(x.device):      # (the choice reads the current device's CU count)
         splits = int(hidden_splits) if hidden_splits else lib.sdetr_ffn_auto_splits(B * rows, F)
-        ws_bytes = lib.sdetr_ffn_workspace_bytes(B * rows, splits) + (B * rows * 512 if splits == 1 else 0)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
-        code = lib.sdetr_ffn_fused_advance_bf16(
-            _hip.stream_ptr(), x.data_ptr(), packed.data_ptr(), b1.data_ptr(), b2.data_ptr(), g.data_ptr(),
-            be.data_ptr(), float(norm.eps), B, rows, 256, F, splits, ws.data_ptr(), ws_bytes, sorted_result.data_ptr(),
-            _hip.ptr(nxt), tokens.data_ptr(), sorted_index.data_ptr(), sorted_index.stride(0), _hip.ptr(count),
-            sorted_result.shape[1], int(next_rows), tokens.shape[1])
-    _hip.check(code, "ffn_fused_advance")
+    ws_bytes = lib.sdetr_ffn_workspace_bytes(B * rows, splits) + (B * rows * 512 if splits == 1 else 0)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    _hip.launch("sdetr_ffn_fused_advance_bf16", lib, x.device, x.data_ptr(), packed.data_ptr(), b1.data_ptr(),
+                b2.data_ptr(), g.data_ptr(), be.data_ptr(), float(norm.eps), B, rows, 256, F, splits, ws.data_ptr(),
+                ws_bytes, sorted_result.data_ptr(), _hip.ptr(nxt), tokens.data_ptr(), sorted_index.data_ptr(),
+                sorted_index.stride(0), _hip.ptr(count), sorted_result.shape[1], int(next_rows), tokens.shape[1],
+                what="ffn_fused_advance")
     return nxt
 
 
@@ -1070,16 +1014,17 @@ def _tail_ffn_operands(output_proj, norm1, linear1, linear2, norm2, class_head=N
             cls_bytes = lib.sdetr_class_head_packed_bytes() if class_head is not None else 0
             packed = torch.empty(tail_bytes + ffn_bytes + cls_bytes, dtype=torch.uint8, device=dev)
             wo = output_proj.weight.detach().contiguous()
-            _hip.check(lib.sdetr_attn_tail_pack_bf16(_hip.stream_ptr(), wo.data_ptr(), 256, packed.data_ptr()), "attn_tail_pack")
+            _hip.launch("sdetr_attn_tail_pack_bf16", lib, dev, wo.data_ptr(), 256, packed.data_ptr(),
+                        what="attn_tail_pack")
             w1, w2 = linear1.weight.detach().contiguous(), linear2.weight.detach().contiguous()
-            _hip.check(lib.sdetr_ffn_pack_bf16(_hip.stream_ptr(), w1.data_ptr(), w2.data_ptr(), 256, F,
-                                               packed.data_ptr() + tail_bytes), "ffn_pack")
+            _hip.launch("sdetr_ffn_pack_bf16", lib, dev, w1.data_ptr(), w2.data_ptr(), 256, F,
+                        packed.data_ptr() + tail_bytes, what="ffn_pack")
             small = [t.detach().float().contiguous() for t in (output_proj.bias, norm1.weight, norm1.bias, linear1.bias,
                                                                linear2.bias, norm2.weight, norm2.bias)]
             if class_head is not None:
                 wc = class_head.weight.detach().contiguous()
-                _hip.check(lib.sdetr_class_head_pack_bf16(_hip.stream_ptr(), wc.data_ptr(), wc.shape[0], 256,
-                                                          packed.data_ptr() + tail_bytes + ffn_bytes), "class_head_pack")
+                _hip.launch("sdetr_class_head_pack_bf16", lib, dev, wc.data_ptr(), wc.shape[0], 256,
+                            packed.data_ptr() + tail_bytes + ffn_bytes, what="class_head_pack")
                 cb = torch.full((96,), float("-inf"), dtype=torch.float32, device=dev)
                 cb[:wc.shape[0]] = class_head.bias.detach().float()
                 small.append(cb)
@@ -1133,17 +1078,16 @@ def attn_tail_ffn_advance(sampled: Tensor, residual: Tensor, output_proj, norm1,
     cls_bias = ops[1][7] if with_score else None
     nxt = torch.empty((B, next_rows, C), dtype=residual.dtype, device=residual.device) if next_rows > 0 else None
     score = torch.empty((B, next_rows), dtype=torch.float32, device=residual.device) if with_score else None
-    with torch.cuda.device(residual.device):
-        ws_bytes = lib.sdetr_ffn_workspace_bytes(B * rows, splits) + (B * rows * 512 if splits == 1 else 0)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=residual.device)
-        code = lib.sdetr_attn_tail_ffn_advance_bf16(
-            _hip.stream_ptr(), sampled.data_ptr(), residual.data_ptr(), packed.data_ptr(), bo.data_ptr(), g1.data_ptr(),
-            be1.data_ptr(), float(norm1.eps), b1.data_ptr(), b2.data_ptr(), g2.data_ptr(), be2.data_ptr(), float(norm2.eps),
-            B, rows, 256, F, splits, ws.data_ptr(), ws_bytes, sorted_result.data_ptr(), _hip.ptr(nxt), tokens.data_ptr(),
-            sorted_index.data_ptr(), sorted_index.stride(0), _hip.ptr(count), sorted_result.shape[1], int(next_rows),
-            tokens.shape[1], _hip.ptr(cls_bias), _hip.ptr(foreground) if with_score else None,
-            (foreground.stride(0) if B > 1 else foreground.shape[1]) if with_score else 0, _hip.ptr(score))
-    _hip.check(code, "attn_tail_ffn_advance")
+    ws_bytes = lib.sdetr_ffn_workspace_bytes(B * rows, splits) + (B * rows * 512 if splits == 1 else 0)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=residual.device)
+    _hip.launch("sdetr_attn_tail_ffn_advance_bf16", lib, residual.device, sampled.data_ptr(), residual.data_ptr(),
+                packed.data_ptr(), bo.data_ptr(), g1.data_ptr(), be1.data_ptr(), float(norm1.eps), b1.data_ptr(),
+                b2.data_ptr(), g2.data_ptr(), be2.data_ptr(), float(norm2.eps), B, rows, 256, F, splits, ws.data_ptr(),
+                ws_bytes, sorted_result.data_ptr(), _hip.ptr(nxt), tokens.data_ptr(), sorted_index.data_ptr(),
+                sorted_index.stride(0), _hip.ptr(count), sorted_result.shape[1], int(next_rows), tokens.shape[1],
+                _hip.ptr(cls_bias), _hip.ptr(foreground) if with_score else None,
+                (foreground.stride(0) if B > 1 else foreground.shape[1]) if with_score else 0, _hip.ptr(score),
+                what="attn_tail_ffn_advance")
     return (nxt, score) if want_score else nxt
 
 
@@ -1157,8 +1101,8 @@ def _packed_linear_bf16(weight: Tensor, bias: Optional[Tensor]):
         npad = (N + 127) // 128 * 128
         with torch.no_grad(), torch.cuda.device(w.device):
             packed = torch.empty(lib.sdetr_linear_packed_bytes(N), dtype=torch.uint8, device=w.device)
-            code = lib.sdetr_linear_pack_bf16(_hip.stream_ptr(), w.data_ptr(), w.stride(0), N, w.shape[1], packed.data_ptr())
-            _hip.check(code, "linear_pack")
+            _hip.launch("sdetr_linear_pack_bf16", lib, w.device, w.data_ptr(), w.stride(0), N, w.shape[1],
+                        packed.data_ptr(), what="linear_pack")
             b = torch.zeros(npad, dtype=torch.float32, device=w.device)
             if bias is not None:
                 b[:N] = bias.detach().float()
@@ -1209,11 +1153,8 @@ def token_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], x_add: Optio
         if x_add.dtype != x.dtype or tuple(x_add.shape) != (B, n, 256):
             raise RuntimeError("token_linear: x_add must match x")
         abs_ = _batch_stride(x_add, "token_linear")
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_token_linear_bf16(_hip.stream_ptr(), x3.data_ptr(), _hip.ptr(x_add), abs_, n, B * n, 256,
-                                                  packed.data_ptr(), b.data_ptr(), N, out.data_ptr(), N,
-                                                  int(group_features))
-    _hip.check(code, "token_linear")
+    _hip.launch("sdetr_token_linear_bf16", x.dtype, x.device, x3.data_ptr(), _hip.ptr(x_add), abs_, n, B * n, 256,
+                packed.data_ptr(), b.data_ptr(), N, out.data_ptr(), N, int(group_features), what="token_linear")
     return out if group_features else out.view(tuple(shape[:-1]) + (N,))
 
 
@@ -1234,11 +1175,8 @@ class RowOrdersJob:
         if self.done:
             return
         j = self.struct
-        with torch.cuda.device(self.device):
-            code = _hip.lib().sdetr_layer_row_orders(_hip.stream_ptr(), j.sorted_index, j.index_batch_stride, j.tile_pos,
-                                                     j.batch, j.spatial_size, j.num_rows, j.num_layers, j.counts, j.order,
-                                                     j.order_batch_stride)
-        _hip.check(code, "layer_row_orders")
+        _hip.launch("sdetr_layer_row_orders", None, self.device, j.sorted_index, j.index_batch_stride, j.tile_pos,
+                    j.batch, j.spatial_size, j.num_rows, j.num_layers, j.counts, j.order, j.order_batch_stride)
         self.done = True
 
 
@@ -1287,11 +1225,9 @@ def value_proj_head_major(value: Tensor, weight: Tensor, bias: Optional[Tensor],
     bordered = None if bordered_levels is None else bordered_struct(bordered_levels, value.device)
     records = Nv if bordered is None else bordered[0].records
     dst = torch.empty((num_groups, B, num_heads, records, 32), dtype=dtype, device=value.device)
-    with torch.cuda.device(value.device):
-        code = _hip.lib(value.dtype).sdetr_value_proj_head_major(
-            _hip.stream_ptr(), value.data_ptr(), packed.data_ptr(), b.data_ptr(), _hip.ptr(pad), B, Nv, 256, num_heads,
-            32, num_groups, dst.data_ptr(), _hip.dtype_code(dtype), None if bordered is None else ctypes.byref(bordered[0]))
-    _hip.check(code, "value_proj_head_major")
+    _hip.launch("sdetr_value_proj_head_major", value.dtype, value.device, value.data_ptr(), packed.data_ptr(),
+                b.data_ptr(), _hip.ptr(pad), B, Nv, 256, num_heads, 32, num_groups, dst.data_ptr(),
+                _hip.dtype_code(dtype), None if bordered is None else ctypes.byref(bordered[0]))
     return dst
 
 
@@ -1306,11 +1242,9 @@ def class_head_max_times(x: Tensor, class_head, scale: Tensor) -> Tensor:
         scale = scale.float().contiguous()
     packed, b = _packed_linear_bf16(class_head.weight, class_head.bias)
     out = torch.empty((B, n), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_class_head_max_times(
-            _hip.stream_ptr(), x.data_ptr(), packed.data_ptr(), b.data_ptr(), 256, class_head.out_features,
-            scale.data_ptr(), scale.stride(0) if B > 1 else max(n, 1), B, n, out.data_ptr())
-    _hip.check(code, "class_head_max_times")
+    _hip.launch("sdetr_class_head_max_times", x.dtype, x.device, x.data_ptr(), packed.data_ptr(), b.data_ptr(), 256,
+                class_head.out_features, scale.data_ptr(), scale.stride(0) if B > 1 else max(n, 1), B, n,
+                out.data_ptr())
     return out
 
 
@@ -1322,10 +1256,8 @@ def masked_fill_min(score: Tensor, mask: Tensor, mins: Tensor) -> Tensor:
         raise RuntimeError("masked_fill_min: fp32 score / mins and a mask of score's shape expected")
     m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
     out = torch.empty_like(score)
-    with torch.cuda.device(score.device):
-        code = _hip.lib().sdetr_masked_fill_min(_hip.stream_ptr(), score.data_ptr(), m.data_ptr(), mins.data_ptr(),
-                                                mins.numel(), score.numel(), out.data_ptr())
-    _hip.check(code, "masked_fill_min")
+    _hip.launch("sdetr_masked_fill_min", None, score.device, score.data_ptr(), m.data_ptr(), mins.data_ptr(),
+                mins.numel(), score.numel(), out.data_ptr())
     return out
 
 
@@ -1345,11 +1277,9 @@ def encoder_reference_points(valid_ratios: Tensor, spatial_shapes: Tensor, level
         rows = index.shape[1]
         ibs = index.stride(0) if B > 1 else rows
     out = torch.empty((B, rows, L, 2), dtype=torch.float32, device=valid_ratios.device)
-    with torch.cuda.device(valid_ratios.device):
-        code = _hip.lib().sdetr_encoder_reference_points(
-            _hip.stream_ptr(), valid_ratios.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            _hip.ptr(index), ibs, B, int(rows), L, out.data_ptr())
-    _hip.check(code, "encoder_reference_points")
+    _hip.launch("sdetr_encoder_reference_points", None, valid_ratios.device, valid_ratios.data_ptr(),
+                spatial_shapes.data_ptr(), level_start_index.data_ptr(), _hip.ptr(index), ibs, B, int(rows), L,
+                out.data_ptr())
     return out
 
 
@@ -1370,10 +1300,8 @@ def encoder_output_proposals(padding_mask: Tensor, level_shapes, want_logit: boo
     keep = torch.empty((B, S), dtype=torch.uint8, device=m.device)
     logit = torch.empty((B, S, 4), dtype=torch.float32, device=m.device) if want_logit else None
     shapes = _host_level_shapes(level_shapes)
-    with torch.cuda.device(m.device):
-        code = _hip.lib().sdetr_encoder_output_proposals(_hip.stream_ptr(), m.data_ptr(), shapes, len(level_shapes), B, S,
-                                                         keep.data_ptr(), _hip.ptr(logit))
-    _hip.check(code, "encoder_output_proposals")
+    _hip.launch("sdetr_encoder_output_proposals", None, m.device, m.data_ptr(), shapes, len(level_shapes), B, S,
+                keep.data_ptr(), _hip.ptr(logit))
     return keep.view(torch.bool), logit
 
 
@@ -1398,11 +1326,9 @@ def grid_nms_topk(topk_index: Tensor, level_shapes, spatial_size: int, iou_thres
     out = torch.empty((B, max_keep), dtype=torch.int64, device=topk_index.device)
     count = torch.empty((B,), dtype=torch.int32, device=topk_index.device)
     shapes = _host_level_shapes(level_shapes)
-    with torch.cuda.device(topk_index.device):
-        code = _hip.lib().sdetr_grid_nms_topk(
-            _hip.stream_ptr(), topk_index.data_ptr(), topk_index.stride(0) if B > 1 else K, shapes, len(level_shapes), B,
-            K, int(spatial_size), nms_neighbourhood(iou_threshold), int(max_keep), out.data_ptr(), count.data_ptr())
-    _hip.check(code, "grid_nms_topk")
+    _hip.launch("sdetr_grid_nms_topk", None, topk_index.device, topk_index.data_ptr(),
+                topk_index.stride(0) if B > 1 else K, shapes, len(level_shapes), B, K, int(spatial_size),
+                nms_neighbourhood(iou_threshold), int(max_keep), out.data_ptr(), count.data_ptr())
     return out, count
 
 
@@ -1417,11 +1343,8 @@ def proposal_refine(delta: Tensor, proposal_logit: Tensor, index: Tensor) -> Ten
     d = delta.contiguous()
     lg = proposal_logit.contiguous()
     out = torch.empty((B, n, 4), dtype=torch.float32, device=d.device)
-    with torch.cuda.device(d.device):
-        code = _hip.lib(d.dtype).sdetr_proposal_refine(_hip.stream_ptr(), d.data_ptr(), _hip.dtype_code(d.dtype), lg.data_ptr(),
-                                                index.data_ptr(), index.stride(0) if B > 1 else n, B, lg.shape[1], n,
-                                                out.data_ptr())
-    _hip.check(code, "proposal_refine")
+    _hip.launch("sdetr_proposal_refine", d.dtype, d.device, d.data_ptr(), _hip.dtype_code(d.dtype), lg.data_ptr(),
+                index.data_ptr(), index.stride(0) if B > 1 else n, B, lg.shape[1], n, out.data_ptr())
     return out
 
 
@@ -1438,11 +1361,9 @@ def attention_heads(q: Tensor, k: Tensor, v: Tensor, num_heads: int) -> Tensor:
         raise RuntimeError("attention_heads: bf16 HIP tensors [B,n,32*heads] with n <= 1152 expected; no CPU fallback")
     B, n, E = q.shape
     out = torch.empty((B, n, E), dtype=q.dtype, device=q.device)
-    with torch.cuda.device(q.device):
-        code = _hip.lib(q.dtype).sdetr_attention_heads_bf16(
-            _hip.stream_ptr(), q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(),
-            v.stride(0), v.stride(1), B, n, num_heads, 32, 1.0 / math.sqrt(32.0), out.data_ptr())
-    _hip.check(code, "attention_heads")
+    _hip.launch("sdetr_attention_heads_bf16", q.dtype, q.device, q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(),
+                k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1), B, n, num_heads, 32,
+                1.0 / math.sqrt(32.0), out.data_ptr(), what="attention_heads")
     return out
 
 
@@ -1459,11 +1380,8 @@ def decoder_query_sine_embed(reference_points: Tensor, valid_ratios: Tensor, num
     L = vr.shape[1]
     embed = torch.empty((B, Nq, 4 * num_pos_feats), dtype=dtype, device=ref.device)
     ref_in = torch.empty((B, Nq, L, 4), dtype=torch.float32, device=ref.device)
-    with torch.cuda.device(ref.device):
-        code = _hip.lib(dtype).sdetr_decoder_query_sine_embed(
-            _hip.stream_ptr(), ref.data_ptr(), vr.data_ptr(), B, Nq, L, int(num_pos_feats), float(temperature),
-            embed.data_ptr(), _hip.dtype_code(dtype), ref_in.data_ptr())
-    _hip.check(code, "decoder_query_sine_embed")
+    _hip.launch("sdetr_decoder_query_sine_embed", dtype, ref.device, ref.data_ptr(), vr.data_ptr(), B, Nq, L,
+                int(num_pos_feats), float(temperature), embed.data_ptr(), _hip.dtype_code(dtype), ref_in.data_ptr())
     return ref_in, embed
 
 
@@ -1489,11 +1407,9 @@ def rows_linear_ln(x: Tensor, linear, norm, residual: Tensor) -> Tensor:
     packed, b = _packed_linear_bf16(linear.weight, linear.bias)
     g, be = _norm_f32(norm)
     out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_rows_linear_ln_bf16(_hip.stream_ptr(), xa.data_ptr(), ra.data_ptr(), xa.numel() // 256,
-                                                           packed.data_ptr(), b.data_ptr(), g.data_ptr(), be.data_ptr(),
-                                                           float(norm.eps), out.data_ptr())
-    _hip.check(code, "rows_linear_ln")
+    _hip.launch("sdetr_rows_linear_ln_bf16", x.dtype, x.device, xa.data_ptr(), ra.data_ptr(), xa.numel() // 256,
+                packed.data_ptr(), b.data_ptr(), g.data_ptr(), be.data_ptr(), float(norm.eps), out.data_ptr(),
+                what="rows_linear_ln")
     return out
 
 
@@ -1524,11 +1440,9 @@ def ref_point_head(reference_points: Tensor, valid_ratios: Tensor, layers, dtype
     p2, b2 = _packed_linear_bf16(layers[1].weight, layers[1].bias)
     pos = torch.empty((B, Nq, 256), dtype=dtype, device=ref.device)
     ref_in = torch.empty((B, Nq, L, 4), dtype=torch.float32, device=ref.device)
-    with torch.cuda.device(ref.device):
-        code = _hip.lib(dtype).sdetr_ref_point_head_bf16(_hip.stream_ptr(), ref.data_ptr(), vr.data_ptr(), B, Nq, L,
-                                                         float(temperature), p1.data_ptr(), b1.data_ptr(), p2.data_ptr(),
-                                                         b2.data_ptr(), pos.data_ptr(), ref_in.data_ptr())
-    _hip.check(code, "ref_point_head")
+    _hip.launch("sdetr_ref_point_head_bf16", dtype, ref.device, ref.data_ptr(), vr.data_ptr(), B, Nq, L,
+                float(temperature), p1.data_ptr(), b1.data_ptr(), p2.data_ptr(), b2.data_ptr(), pos.data_ptr(),
+                ref_in.data_ptr(), what="ref_point_head")
     return ref_in, pos
 
 
@@ -1554,10 +1468,8 @@ def rows_linear(x: Tensor, weight: Tensor, bias: Tensor, pos: Optional[Tensor] =
         pa = pos if pos.is_contiguous() else pos.contiguous()
     packed, b = _packed_linear_bf16(weight, bias)
     out = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_rows_linear_bf16(_hip.stream_ptr(), xa.data_ptr(), _hip.ptr(pa), xa.numel() // 256,
-                                                        int(pos_features), packed.data_ptr(), b.data_ptr(), N, out.data_ptr(), N)
-    _hip.check(code, "rows_linear")
+    _hip.launch("sdetr_rows_linear_bf16", x.dtype, x.device, xa.data_ptr(), _hip.ptr(pa), xa.numel() // 256,
+                int(pos_features), packed.data_ptr(), b.data_ptr(), N, out.data_ptr(), N, what="rows_linear")
     return out
 
 
@@ -1605,12 +1517,10 @@ def decoder_head(query: Tensor, norm, class_head, bbox_layers, reference_points:
     ncls = class_head.out_features
     logits = torch.empty(lead + (ncls,), dtype=query.dtype, device=query.device)
     boxes = torch.empty(((2 if two_sources else 1),) + lead + (4,), dtype=torch.float32, device=query.device)
-    with torch.cuda.device(query.device):
-        code = _hip.lib(query.dtype).sdetr_decoder_head_bf16(
-            _hip.stream_ptr(), q.data_ptr(), rows, g.data_ptr(), b.data_ptr(), float(norm.eps), pc.data_ptr(), bc.data_ptr(),
-            ncls, ops[0][0].data_ptr(), ops[0][1].data_ptr(), ops[1][0].data_ptr(), ops[1][1].data_ptr(), ops[2][0].data_ptr(),
-            ops[2][1].data_ptr(), ref.data_ptr(), float(eps), 1 if two_sources else 0, logits.data_ptr(), ncls, boxes.data_ptr())
-    _hip.check(code, "decoder_head")
+    _hip.launch("sdetr_decoder_head_bf16", query.dtype, query.device, q.data_ptr(), rows, g.data_ptr(), b.data_ptr(),
+                float(norm.eps), pc.data_ptr(), bc.data_ptr(), ncls, ops[0][0].data_ptr(), ops[0][1].data_ptr(),
+                ops[1][0].data_ptr(), ops[1][1].data_ptr(), ops[2][0].data_ptr(), ops[2][1].data_ptr(), ref.data_ptr(),
+                float(eps), 1 if two_sources else 0, logits.data_ptr(), ncls, boxes.data_ptr(), what="decoder_head")
     return logits, boxes
 
 
@@ -1640,9 +1550,8 @@ def _packed_linear_512(weight: Tensor, bias: Tensor):
         with torch.no_grad(), torch.cuda.device(w.device):
             packed = torch.empty(2 * half, dtype=torch.uint8, device=w.device)
             for i in range(2):
-                code = lib.sdetr_linear_pack_bf16(_hip.stream_ptr(), w.data_ptr() + i * 256 * w.element_size(), w.stride(0),
-                                                  256, 256, packed.data_ptr() + i * half)
-                _hip.check(code, "linear_pack")
+                _hip.launch("sdetr_linear_pack_bf16", lib, w.device, w.data_ptr() + i * 256 * w.element_size(),
+                            w.stride(0), 256, 256, packed.data_ptr() + i * half, what="linear_pack")
             return packed, bias.detach().float().contiguous()
     return derived(weight, "token_linear_512", (weight, bias), build)
 
@@ -1669,11 +1578,9 @@ def mlp_rows(x: Tensor, layers, x_second: Optional[Tensor] = None) -> Tensor:
     out = torch.empty(((2,) + lead if xb is not None else lead) + (n_out,), dtype=x.dtype, device=x.device)
     ops = [(_packed_linear_512 if l.in_features == 512 else _packed_linear_bf16)(l.weight, l.bias) for l in layers]
     p3, b3 = ops[2] if len(layers) == 3 else (None, None)
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_mlp_rows_bf16(
-            _hip.stream_ptr(), xa.data_ptr(), _hip.ptr(xb), rows_a, rows, K, ops[0][0].data_ptr(), ops[0][1].data_ptr(),
-            ops[1][0].data_ptr(), ops[1][1].data_ptr(), _hip.ptr(p3), _hip.ptr(b3), n_out, out.data_ptr(), n_out)
-    _hip.check(code, "mlp_rows")
+    _hip.launch("sdetr_mlp_rows_bf16", x.dtype, x.device, xa.data_ptr(), _hip.ptr(xb), rows_a, rows, K,
+                ops[0][0].data_ptr(), ops[0][1].data_ptr(), ops[1][0].data_ptr(), ops[1][1].data_ptr(), _hip.ptr(p3),
+                _hip.ptr(b3), n_out, out.data_ptr(), n_out, what="mlp_rows")
     return out
 
 
@@ -1689,10 +1596,8 @@ def box_refine(delta: Tensor, reference_points: Tensor, eps: float = 1e-3) -> Te
         raise RuntimeError("box_refine: delta [(G,)B,Nq,4] fp32 | bf16 against boxes [B,Nq,4] expected")
     d = delta.detach().contiguous()
     out = torch.empty(d.shape, dtype=torch.float32, device=d.device)
-    with torch.cuda.device(d.device):
-        code = _hip.lib(d.dtype).sdetr_box_refine(_hip.stream_ptr(), d.data_ptr(), _hip.dtype_code(d.dtype), 4, ref.data_ptr(),
-                                           n, d.numel() // (4 * n), float(eps), out.data_ptr())
-    _hip.check(code, "box_refine")
+    _hip.launch("sdetr_box_refine", d.dtype, d.device, d.data_ptr(), _hip.dtype_code(d.dtype), 4, ref.data_ptr(), n,
+                d.numel() // (4 * n), float(eps), out.data_ptr())
     return out
 
 
@@ -1731,8 +1636,8 @@ def _class_head_fragments(class_head):
         with torch.no_grad(), torch.cuda.device(w.device):
             packed = torch.empty(lib.sdetr_class_head_packed_bytes(), dtype=torch.uint8, device=w.device)
             wc = w.detach().contiguous()
-            _hip.check(lib.sdetr_class_head_pack_bf16(_hip.stream_ptr(), wc.data_ptr(), wc.shape[0], 256, packed.data_ptr()),
-                       "class_head_pack")
+            _hip.launch("sdetr_class_head_pack_bf16", lib, w.device, wc.data_ptr(), wc.shape[0], 256, packed.data_ptr(),
+                        what="class_head_pack")
             cb = torch.full((96,), float("-inf"), dtype=torch.float32, device=w.device)
             cb[:wc.shape[0]] = b.detach().float()
         return packed, cb
@@ -1791,14 +1696,10 @@ def encoder_prepare_sorted(tokens: Tensor, pos: Tensor, score, sorted_index: Ten
     if with_cls:
         packed, cb = _class_head_fragments(class_head)
         cls = torch.empty((B, n), dtype=torch.float32, device=tokens.device)
-        with torch.cuda.device(tokens.device):
-            code = _hip.lib(tokens.dtype).sdetr_encoder_prepare_sorted_scored(_hip.stream_ptr(), *args, packed.data_ptr(),
-                                                                              cb.data_ptr(), cls.data_ptr())
-        _hip.check(code, "encoder_prepare_sorted")
+        _hip.launch("sdetr_encoder_prepare_sorted_scored", tokens.dtype, tokens.device, *args, packed.data_ptr(),
+                    cb.data_ptr(), cls.data_ptr(), what="encoder_prepare_sorted")
         return q, ps, fg, ref, cls
-    with torch.cuda.device(tokens.device):
-        code = _hip.lib().sdetr_encoder_prepare_sorted(_hip.stream_ptr(), *args)
-    _hip.check(code, "encoder_prepare_sorted")
+    _hip.launch("sdetr_encoder_prepare_sorted", None, tokens.device, *args)
     return q, ps, fg, ref
 
 
@@ -1825,12 +1726,10 @@ def token_linear_ln(x: Tensor, linear, norm, residual: Tensor, scatter_index: Op
         out, out_rows = scatter_into, scatter_into.shape[1]
     else:
         out = torch.empty((B, n, 256), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_token_linear_ln_bf16(
-            _hip.stream_ptr(), x.data_ptr(), residual.data_ptr(), _batch_stride(residual, "token_linear_ln"), n, B * n,
-            256, packed.data_ptr(), b.data_ptr(), g.data_ptr(), be.data_ptr(), float(norm.eps), out.data_ptr(),
-            _hip.ptr(scatter_index), out_rows)
-    _hip.check(code, "token_linear_ln")
+    _hip.launch("sdetr_token_linear_ln_bf16", x.dtype, x.device, x.data_ptr(), residual.data_ptr(),
+                _batch_stride(residual, "token_linear_ln"), n, B * n, 256, packed.data_ptr(), b.data_ptr(),
+                g.data_ptr(), be.data_ptr(), float(norm.eps), out.data_ptr(), _hip.ptr(scatter_index), out_rows,
+                what="token_linear_ln")
     return out
 
 
@@ -1846,10 +1745,8 @@ def merge_sorted_desc(score: Tensor, payload: Tensor, segment_start, want_scores
     seg = (ctypes.c_int * len(segment_start))(*[int(v) for v in segment_start])
     out_index = torch.empty_like(payload)
     out_score = torch.empty_like(score) if want_scores else None
-    with torch.cuda.device(score.device):
-        code = _hip.lib().sdetr_merge_sorted_desc(_hip.stream_ptr(), score.data_ptr(), payload.data_ptr(), seg,
-                                                  len(segment_start), B, n, out_index.data_ptr(), _hip.ptr(out_score))
-    _hip.check(code, "merge_sorted_desc")
+    _hip.launch("sdetr_merge_sorted_desc", None, score.device, score.data_ptr(), payload.data_ptr(), seg,
+                len(segment_start), B, n, out_index.data_ptr(), _hip.ptr(out_score))
     return out_score, out_index
 
 
@@ -1880,9 +1777,8 @@ def neck_pack_conv3x3(weight: Tensor, act: torch.dtype = torch.bfloat16) -> Opti
     if nbytes == 0:
         return None
     packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        code = lib.sdetr_neck_pack_conv3x3_bf16(_hip.stream_ptr(), weight.data_ptr(), G, ci, co, packed.data_ptr())
-    _hip.check(code, "neck_pack_conv3x3")
+    _hip.launch("sdetr_neck_pack_conv3x3_bf16", lib, weight.device, weight.data_ptr(), G, ci, co, packed.data_ptr(),
+                what="neck_pack_conv3x3")
     return packed
 
 
@@ -1904,17 +1800,12 @@ def neck_conv3x3(x: Tensor, height: int, width: int, weight: Tensor, bias: Optio
     out = torch.empty((B, ho * wo, G * co), dtype=x.dtype, device=x.device)
     if packed is not None and _hip.is_act16(x.dtype) and ld % 8 == 0 and x.data_ptr() % 16 == 0:
         _hip.require_device("neck_conv3x3", packed=packed)
-        with torch.cuda.device(x.device):
-            code = _hip.lib(x.dtype).sdetr_neck_conv3x3_mfma_bf16(_hip.stream_ptr(), x.data_ptr(), B, height, width, ld,
-                                                           packed.data_ptr(), _hip.ptr(bias), G, ci, co, int(stride),
-                                                           int(bool(activation)), out.data_ptr())
-        _hip.check(code, "neck_conv3x3_mfma")
+        _hip.launch("sdetr_neck_conv3x3_mfma_bf16", x.dtype, x.device, x.data_ptr(), B, height, width, ld,
+                    packed.data_ptr(), _hip.ptr(bias), G, ci, co, int(stride), int(bool(activation)), out.data_ptr(),
+                    what="neck_conv3x3_mfma")
         return out
-    with torch.cuda.device(x.device):
-        code = _hip.lib(x.dtype).sdetr_neck_conv3x3(_hip.stream_ptr(), x.data_ptr(), _hip.dtype_code(x.dtype), B, height, width,
-                                             ld, weight.data_ptr(), _hip.ptr(bias), G, ci, co, int(stride),
-                                             int(bool(activation)), out.data_ptr())
-    _hip.check(code, "neck_conv3x3")
+    _hip.launch("sdetr_neck_conv3x3", x.dtype, x.device, x.data_ptr(), _hip.dtype_code(x.dtype), B, height, width, ld,
+                weight.data_ptr(), _hip.ptr(bias), G, ci, co, int(stride), int(bool(activation)), out.data_ptr())
     return out
 
 
@@ -1935,11 +1826,8 @@ def neck_combine(a: Tensor, height: int, width: int, up: Optional[Tensor] = None
         if bias.dtype != torch.float32 or bias.numel() != C:
             raise RuntimeError("neck_combine: bias must be fp32 [C]")
     out = torch.empty((B, height * width, C), dtype=a.dtype, device=a.device)
-    with torch.cuda.device(a.device):
-        code = _hip.lib(a.dtype).sdetr_neck_combine(_hip.stream_ptr(), a.data_ptr(), lda, _hip.ptr(up), ldu, uh, uw,
-                                             _hip.ptr(bias), _hip.dtype_code(a.dtype), B, height, width, C,
-                                             int(bool(activation)), out.data_ptr(), C)
-    _hip.check(code, "neck_combine")
+    _hip.launch("sdetr_neck_combine", a.dtype, a.device, a.data_ptr(), lda, _hip.ptr(up), ldu, uh, uw, _hip.ptr(bias),
+                _hip.dtype_code(a.dtype), B, height, width, C, int(bool(activation)), out.data_ptr(), C)
     return out
 
 
@@ -1965,12 +1853,9 @@ def neck_gate_shortcut(y: Tensor, mask_weight: Tensor, squeeze_weight: Tensor, e
     ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=y.device)
     gate = torch.empty((B, C), dtype=torch.float32, device=y.device)
     out = torch.empty_like(y)
-    with torch.cuda.device(y.device):
-        code = lib.sdetr_neck_gate_shortcut(_hip.stream_ptr(), y.data_ptr(), _hip.dtype_code(y.dtype), B, N, C,
-                                            mask_weight.data_ptr(), squeeze_weight.data_ptr(), excite_weight.data_ptr(),
-                                            R, shortcut.data_ptr(), ld1, _hip.ptr(shortcut2), ld2, ws.data_ptr(),
-                                            ws_bytes, gate.data_ptr(), out.data_ptr())
-    _hip.check(code, "neck_gate_shortcut")
+    _hip.launch("sdetr_neck_gate_shortcut", lib, y.device, y.data_ptr(), _hip.dtype_code(y.dtype), B, N, C,
+                mask_weight.data_ptr(), squeeze_weight.data_ptr(), excite_weight.data_ptr(), R, shortcut.data_ptr(),
+                ld1, _hip.ptr(shortcut2), ld2, ws.data_ptr(), ws_bytes, gate.data_ptr(), out.data_ptr())
     return out
 
 
@@ -2028,13 +1913,11 @@ def topk_select_inproj(score: Tensor, k: int, query: Tensor, pos: Tensor, mha, o
     job = orders_job if orders_job is not None and not orders_job.done and orders_job.device == dev else None
     cand_bytes = lib.sdetr_topk_select_candidate_bytes(B, n, k)      # (rows beyond one workgroup's sort: their slices' top-k)
     cand = torch.empty(cand_bytes, dtype=torch.uint8, device=dev) if cand_bytes else None
-    with torch.cuda.device(dev):
-        code = lib.sdetr_topk_select_inproj_bf16(
-            _hip.stream_ptr(), score.data_ptr(), B, n, k, sel.data_ptr(), query.data_ptr(),
-            query.stride(0) if B > 1 else n * 256, pos.data_ptr(), pos.stride(0) if B > 1 else pos.shape[1] * 256,
-            mha.in_proj_weight.data_ptr(), mha.in_proj_bias.data_ptr(), ws.data_ptr(), ws.numel(), hint.data_ptr(),
-            hint.stride(0), None if job is None else ctypes.byref(job.struct), _hip.ptr(cand), cand_bytes)
-    _hip.check(code, "topk_select_inproj")
+    _hip.launch("sdetr_topk_select_inproj_bf16", lib, dev, score.data_ptr(), B, n, k, sel.data_ptr(), query.data_ptr(),
+                query.stride(0) if B > 1 else n * 256, pos.data_ptr(), pos.stride(0) if B > 1 else pos.shape[1] * 256,
+                mha.in_proj_weight.data_ptr(), mha.in_proj_bias.data_ptr(), ws.data_ptr(), ws.numel(), hint.data_ptr(),
+                hint.stride(0), None if job is None else ctypes.byref(job.struct), _hip.ptr(cand), cand_bytes,
+                what="topk_select_inproj")
     if job is not None:
         job.done = True
     return SelectedInProjection(sel, ws, hint)
@@ -2068,31 +1951,28 @@ def topk_self_attention_(query: Tensor, pos: Tensor, selected: Tensor, mha, norm
     carried = (projection is not None and 289 <= N <= 320 and query.is_contiguous()
                and token_linear_applies(query, projection[0]) and tuple(projection[0].shape) == (384, 256)
                and projection[0].is_contiguous())
-    with torch.cuda.device(query.device):
-        if carried:
-            w, b = projection
-            packed, b_pad = _packed_linear_bf16(w, b)
-            slab = torch.empty((B, 8, rows, 48), dtype=query.dtype, device=query.device)
-            # marks of the selected rows for the projection part of the launch: UNINITIALISED on purpose -- a mark m
-            # counts only if selected[b][m - 1] is the row it sits on, which no garbage value can fake, and the
-            # in-projection writes the true marks before anything reads them
-            hint = inprojection.hint if inprojection is not None else torch.empty((B, rows), dtype=torch.int32, device=query.device)
-            code = lib.sdetr_topk_attention_with_projection_bf16(
-                _hip.stream_ptr(), query.data_ptr(), qbs, pos.data_ptr(), pbs, selected.data_ptr(), B, rows, N,
-                mha.in_proj_weight.data_ptr(), mha.in_proj_bias.data_ptr(), mha.out_proj.weight.data_ptr(),
-                mha.out_proj.bias.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps),
-                ws.data_ptr(), ws.numel(), w.data_ptr(), packed.data_ptr(), b_pad.data_ptr(), slab.data_ptr(),
-                hint.data_ptr(), hint.stride(0),
-                _fragment_order(mha.out_proj.weight, 32).data_ptr() if mha.out_proj.weight.is_contiguous() else None,
-                _fragment_order(w, 48).data_ptr(), 1 if inprojection is not None else 0)
-            _hip.check(code, "topk_self_attention_")
-            return slab
-        if inprojection is not None:
-            raise RuntimeError("topk_self_attention_: an in-projection from the selection's launch needs the carried form")
-        code = lib.sdetr_topk_attention_bf16(
-            _hip.stream_ptr(), query.data_ptr(), qbs, pos.data_ptr(), pbs, selected.data_ptr(), B, rows, N,
-            mha.in_proj_weight.data_ptr(), mha.in_proj_bias.data_ptr(), mha.out_proj.weight.data_ptr(),
-            mha.out_proj.bias.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps), 256, 8,
-            ws.data_ptr(), ws.numel())
-    _hip.check(code, "topk_self_attention_")
+    if carried:
+        w, b = projection
+        packed, b_pad = _packed_linear_bf16(w, b)
+        slab = torch.empty((B, 8, rows, 48), dtype=query.dtype, device=query.device)
+        # marks of the selected rows for the projection part of the launch: UNINITIALISED on purpose -- a mark m
+        # counts only if selected[b][m - 1] is the row it sits on, which no garbage value can fake, and the
+        # in-projection writes the true marks before anything reads them
+        hint = inprojection.hint if inprojection is not None else torch.empty((B, rows), dtype=torch.int32, device=query.device)
+        _hip.launch("sdetr_topk_attention_with_projection_bf16", lib, query.device, query.data_ptr(), qbs,
+                    pos.data_ptr(), pbs, selected.data_ptr(), B, rows, N, mha.in_proj_weight.data_ptr(),
+                    mha.in_proj_bias.data_ptr(), mha.out_proj.weight.data_ptr(), mha.out_proj.bias.data_ptr(),
+                    norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps), ws.data_ptr(), ws.numel(),
+                    w.data_ptr(), packed.data_ptr(), b_pad.data_ptr(), slab.data_ptr(), hint.data_ptr(),
+                    hint.stride(0),
+                    _fragment_order(mha.out_proj.weight, 32).data_ptr() if mha.out_proj.weight.is_contiguous() else None,
+                    _fragment_order(w, 48).data_ptr(), 1 if inprojection is not None else 0,
+                    what="topk_self_attention_")
+        return slab
+    if inprojection is not None:
+        raise RuntimeError("topk_self_attention_: an in-projection from the selection's launch needs the carried form")
+    _hip.launch("sdetr_topk_attention_bf16", lib, query.device, query.data_ptr(), qbs, pos.data_ptr(), pbs,
+                selected.data_ptr(), B, rows, N, mha.in_proj_weight.data_ptr(), mha.in_proj_bias.data_ptr(),
+                mha.out_proj.weight.data_ptr(), mha.out_proj.bias.data_ptr(), norm.weight.data_ptr(),
+                norm.bias.data_ptr(), float(norm.eps), 256, 8, ws.data_ptr(), ws.numel(), what="topk_self_attention_")
     return None if projection is not None else query

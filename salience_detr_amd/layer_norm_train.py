@@ -35,11 +35,9 @@ class _AddLayerNorm(Function):
         z = torch.empty_like(x2) if r2 is not None else None
         stats = torch.empty((2, rows), dtype=torch.float32, device=x.device)
         w, b = weight.contiguous(), bias.contiguous()
-        with torch.cuda.device(x.device):
-            code = _hip.lib().sdetr_layer_norm_train_forward_f32(
-                _hip.stream_ptr(), x2.data_ptr(), _hip.ptr(r2), w.data_ptr(), b.data_ptr(), float(eps), rows, C,
-                _hip.ptr(z), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr())
-        _hip.check(code, "layer_norm_train_forward")
+        _hip.launch("sdetr_layer_norm_train_forward_f32", None, x.device, x2.data_ptr(), _hip.ptr(r2), w.data_ptr(),
+                    b.data_ptr(), float(eps), rows, C, _hip.ptr(z), y.data_ptr(), stats[0].data_ptr(),
+                    stats[1].data_ptr(), what="layer_norm_train_forward")
         ctx.save_for_backward(x2 if z is None else z, stats, w)
         ctx.has_residual = residual is not None
         ctx.shape = x.shape
@@ -52,11 +50,9 @@ class _AddLayerNorm(Function):
         g2 = gy.contiguous().view(rows, C)
         dz = torch.empty_like(z)
         dwb = zero_arena.zeros((2, C), dtype=torch.float32, device=z.device)
-        with torch.cuda.device(z.device):
-            code = _hip.lib().sdetr_layer_norm_train_backward_f32(
-                _hip.stream_ptr(), g2.data_ptr(), z.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), w.data_ptr(),
-                rows, C, dz.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr())
-        _hip.check(code, "layer_norm_train_backward")
+        _hip.launch("sdetr_layer_norm_train_backward_f32", None, z.device, g2.data_ptr(), z.data_ptr(),
+                    stats[0].data_ptr(), stats[1].data_ptr(), w.data_ptr(), rows, C, dz.data_ptr(), dwb[0].data_ptr(),
+                    dwb[1].data_ptr(), what="layer_norm_train_backward")
         dz = dz.view(ctx.shape)
         return dz, (dz if ctx.has_residual else None), dwb[0], dwb[1], None
 

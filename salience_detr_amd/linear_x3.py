@@ -47,12 +47,10 @@ def gemm_x3(a: Tensor, a_kmajor: bool, b: Tensor, b_kmajor: bool, M: int, N: int
         if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != M * N or out.device != a.device:
             raise RuntimeError("gemm_x3: out must be a contiguous fp32 tensor of M * N elements on the operands' device")
         c = out.view(M, N)
-    with torch.cuda.device(a.device):
-        code = _hip.lib().sdetr_gemm_x3_epilogue_f32(
-            _hip.stream_ptr(), a.data_ptr(), a.stride(0), int(a_kmajor), b.data_ptr(), b.stride(0), int(b_kmajor),
-            c.data_ptr(), c.stride(0), M, N, K, _hip.ptr(bias), int(reduction_splits), _hip.ptr(a_row_sum),
-            int(epilogue), _hip.ptr(gate) if epilogue == EPI_GATE else None, gate.stride(0) if epilogue == EPI_GATE else 0)
-    _hip.check(code, "gemm_x3")
+    _hip.launch("sdetr_gemm_x3_epilogue_f32", None, a.device, a.data_ptr(), a.stride(0), int(a_kmajor), b.data_ptr(),
+                b.stride(0), int(b_kmajor), c.data_ptr(), c.stride(0), M, N, K, _hip.ptr(bias), int(reduction_splits),
+                _hip.ptr(a_row_sum), int(epilogue), _hip.ptr(gate) if epilogue == EPI_GATE else None,
+                gate.stride(0) if epilogue == EPI_GATE else 0, what="gemm_x3")
     return c if out is None else out
 
 
@@ -65,10 +63,8 @@ def presplit(w: Tensor, transpose: bool = False) -> Tensor:
         raise RuntimeError("presplit: 2-d fp32 tensor with a contiguous last dimension expected")
     R, C = w.shape
     out = torch.empty((3, C, R) if transpose else (3, R, C), dtype=torch.bfloat16, device=w.device)
-    with torch.cuda.device(w.device):
-        code = _hip.lib().sdetr_gemm_x3_presplit(_hip.stream_ptr(), w.data_ptr(), w.stride(0), R, C, int(transpose),
-                                                 out.data_ptr())
-    _hip.check(code, "presplit")
+    _hip.launch("sdetr_gemm_x3_presplit", None, w.device, w.data_ptr(), w.stride(0), R, C, int(transpose),
+                out.data_ptr(), what="presplit")
     return out
 
 
@@ -92,11 +88,8 @@ def gemm_x3_presplit_b(a: Tensor, a_kmajor: bool, b_planes: Tensor, M: int, N: i
             or tuple(a.shape) != ((M, K) if a_kmajor else (K, M))):
         raise RuntimeError("gemm_x3_presplit_b: fp32 a, contiguous bf16 planes [3, N, K] expected")
     c = torch.empty((M, N), dtype=torch.float32, device=a.device) if out is None else out.view(M, N)
-    with torch.cuda.device(a.device):
-        code = _hip.lib().sdetr_gemm_x3_f32(_hip.stream_ptr(), a.data_ptr(), a.stride(0), int(a_kmajor),
-                                            b_planes.data_ptr(), K, 2, c.data_ptr(), c.stride(0), M, N, K,
-                                            _hip.ptr(bias), 1, None)
-    _hip.check(code, "gemm_x3")
+    _hip.launch("sdetr_gemm_x3_f32", None, a.device, a.data_ptr(), a.stride(0), int(a_kmajor), b_planes.data_ptr(), K,
+                2, c.data_ptr(), c.stride(0), M, N, K, _hip.ptr(bias), 1, None, what="gemm_x3")
     return c if out is None else out
 
 

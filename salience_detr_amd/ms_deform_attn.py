@@ -73,11 +73,9 @@ def ms_deform_attn_forward(value: Tensor, spatial_shapes: Tensor, level_start_in
     B, Nv, M, D, L, Nq, P = _op_dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                                      im2col_step, "ms_deform_attn_forward")
     out = torch.empty((B, Nq, M * D), dtype=value.dtype, device=value.device)
-    fn = _hip.lib().sdetr_msda_im2col_f32 if value.dtype == torch.float32 else _hip.lib().sdetr_msda_im2col_f64
-    with torch.cuda.device(value.device):
-        code = fn(_hip.stream_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                  sampling_loc.data_ptr(), attn_weight.data_ptr(), B, Nv, M, D, L, Nq, P, out.data_ptr())
-    _hip.check(code, "ms_deform_attn_forward")
+    _hip.launch("sdetr_msda_im2col_f32" if value.dtype == torch.float32 else "sdetr_msda_im2col_f64", None, value.device,
+                value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+                attn_weight.data_ptr(), B, Nv, M, D, L, Nq, P, out.data_ptr(), what="ms_deform_attn_forward")
     return out
 
 
@@ -114,17 +112,16 @@ def ms_deform_attn_backward(value: Tensor, spatial_shapes: Tensor, level_start_i
     common = (grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
               sampling_loc.data_ptr(), attn_weight.data_ptr(), B, Nv, M, D, L, Nq, P, grad_value.data_ptr(),
               grad_loc.data_ptr(), grad_aw.data_ptr())
-    with torch.cuda.device(value.device):
-        if (lds_backward and value.dtype == torch.float32 and Nq >= lds_backward_min_queries
-                and lib.sdetr_msda_col2im_lds_supported(M, D, L, P, Nv)):
-            # grad_value accumulated in LDS windows (msda_backward_tiled.hip); scratch for the query bucketing
-            nbytes = lib.sdetr_msda_col2im_lds_workspace_bytes(B, Nq, M, L)
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
-            code = lib.sdetr_msda_col2im_lds_f32(_hip.stream_ptr(), *common, workspace.data_ptr(), nbytes)
-        else:
-            fn = lib.sdetr_msda_col2im_f32 if value.dtype == torch.float32 else lib.sdetr_msda_col2im_f64
-            code = fn(_hip.stream_ptr(), *common)
-    _hip.check(code, "ms_deform_attn_backward")
+    if (lds_backward and value.dtype == torch.float32 and Nq >= lds_backward_min_queries
+            and lib.sdetr_msda_col2im_lds_supported(M, D, L, P, Nv)):
+        # grad_value accumulated in LDS windows (msda_backward_tiled.hip); scratch for the query bucketing
+        nbytes = lib.sdetr_msda_col2im_lds_workspace_bytes(B, Nq, M, L)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
+        _hip.launch("sdetr_msda_col2im_lds_f32", lib, value.device, *common, workspace.data_ptr(), nbytes,
+                    what="ms_deform_attn_backward")
+    else:
+        _hip.launch("sdetr_msda_col2im_f32" if value.dtype == torch.float32 else "sdetr_msda_col2im_f64", lib,
+                    value.device, *common, what="ms_deform_attn_backward")
     return [grad_value, grad_loc, grad_aw]
 
 
@@ -179,12 +176,9 @@ def value_to_head_major(value_proj_out: Tensor, key_padding_mask: Optional[Tenso
     if key_padding_mask is not None:
         _hip.require_device("value_to_head_major", key_padding_mask=key_padding_mask)
         mask_u8 = key_padding_mask.view(torch.uint8) if key_padding_mask.dtype == torch.bool else key_padding_mask
-    with torch.cuda.device(dst.device):
-        code = _hip.lib(value_proj_out.dtype).sdetr_value_to_head_major(
-            _hip.stream_ptr(), value_proj_out.data_ptr(), _hip.dtype_code(value_proj_out.dtype),
-            value_proj_out.stride(1), _hip.ptr(mask_u8), B, Nv, num_heads, D, num_groups, dst.data_ptr(),
-            _hip.dtype_code(out_dtype))
-    _hip.check(code, "value_to_head_major")
+    _hip.launch("sdetr_value_to_head_major", value_proj_out.dtype, dst.device, value_proj_out.data_ptr(),
+                _hip.dtype_code(value_proj_out.dtype), value_proj_out.stride(1), _hip.ptr(mask_u8), B, Nv, num_heads, D,
+                num_groups, dst.data_ptr(), _hip.dtype_code(out_dtype))
     return dst
 
 
@@ -223,13 +217,11 @@ def msda_fused_forward(value_hm: Tensor, spatial_shapes: Tensor, level_start_ind
     ref_bs = reference_points.stride(0) if (B > 1 and Nq > 0) else 0
     out_dtype = out_dtype or proj.dtype
     out = torch.empty((B, Nq, M * D), dtype=out_dtype, device=value_hm.device)
-    with torch.cuda.device(out.device):
-        code = _hip.lib(proj.dtype).sdetr_msda_fused_forward(
-            _hip.stream_ptr(), value_hm.data_ptr(), _hip.dtype_code(value_hm.dtype), spatial_shapes.data_ptr(),
-            level_start_index.data_ptr(), reference_points.data_ptr(), reference_points.shape[-1], ref_bs,
-            proj.data_ptr(), _hip.dtype_code(proj.dtype), proj_stride, 1 if proj_head_major else 0, _hip.ptr(order),
-            B, Nv, M, D, num_levels, Nq, num_points, out.data_ptr(), _hip.dtype_code(out_dtype))
-    _hip.check(code, "msda_fused_forward")
+    _hip.launch("sdetr_msda_fused_forward", proj.dtype, out.device, value_hm.data_ptr(),
+                _hip.dtype_code(value_hm.dtype), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                reference_points.data_ptr(), reference_points.shape[-1], ref_bs, proj.data_ptr(),
+                _hip.dtype_code(proj.dtype), proj_stride, 1 if proj_head_major else 0, _hip.ptr(order), B, Nv, M, D,
+                num_levels, Nq, num_points, out.data_ptr(), _hip.dtype_code(out_dtype))
     return out
 
 
@@ -283,12 +275,10 @@ def msda_resident_forward(value_hm: Tensor, level_shapes, reference_points: Tens
     out_dtype = out_dtype or proj_hm.dtype
     out = torch.empty((B, Nq, M * D), dtype=out_dtype, device=value_hm.device)
     hw = (ctypes.c_int32 * 8)(*[int(v) for s in level_shapes for v in s])
-    with torch.cuda.device(out.device):
-        code = _hip.lib(proj_hm.dtype).sdetr_msda_resident_forward_ex(
-            _hip.stream_ptr(), value_hm.data_ptr(), _hip.dtype_code(value_hm.dtype), hw, reference_points.data_ptr(),
-            reference_points.shape[-1], ref_bs, proj_hm.data_ptr(), B, Nv, M, Nq, out.data_ptr(),
-            _hip.dtype_code(out_dtype), int(chunks), -1 if image_lanes is None else int(image_lanes))
-    _hip.check(code, "msda_resident_forward")
+    _hip.launch("sdetr_msda_resident_forward_ex", proj_hm.dtype, out.device, value_hm.data_ptr(),
+                _hip.dtype_code(value_hm.dtype), hw, reference_points.data_ptr(), reference_points.shape[-1], ref_bs,
+                proj_hm.data_ptr(), B, Nv, M, Nq, out.data_ptr(), _hip.dtype_code(out_dtype), int(chunks),
+                -1 if image_lanes is None else int(image_lanes), what="msda_resident_forward")
     return out
 
 
@@ -446,14 +436,13 @@ def msda_bordered_forward(value_bordered: Tensor, level_shapes, reference_points
     out_dtype = out_dtype or proj_hm.dtype
     out = torch.empty((B, Nq, M * D), dtype=out_dtype, device=value_bordered.device)
     hw = (ctypes.c_int32 * 8)(*[int(v) for s in level_shapes for v in s])
-    with torch.cuda.device(out.device):
-        code = _hip.lib(proj_hm.dtype).sdetr_msda_bordered_forward_ex(
-            _hip.stream_ptr(), value_bordered.data_ptr(), _hip.dtype_code(value_bordered.dtype), hw,
-            reference_points.data_ptr(), reference_points.shape[-1], ref_bs, proj_hm.data_ptr(), _hip.ptr(row_order),
-            (row_order.stride(0) if B > 1 else Nq) if row_order is not None else 0, B, Np, M, Nq, out.data_ptr(),
-            _hip.dtype_code(out_dtype), int(chunks), int(accumulate), -1 if image_lanes is None else int(image_lanes),
-            -1 if l2_warmup is None else int(l2_warmup))
-    _hip.check(code, "msda_bordered_forward")
+    _hip.launch("sdetr_msda_bordered_forward_ex", proj_hm.dtype, out.device, value_bordered.data_ptr(),
+                _hip.dtype_code(value_bordered.dtype), hw, reference_points.data_ptr(), reference_points.shape[-1],
+                ref_bs, proj_hm.data_ptr(), _hip.ptr(row_order),
+                (row_order.stride(0) if B > 1 else Nq) if row_order is not None else 0, B, Np, M, Nq, out.data_ptr(),
+                _hip.dtype_code(out_dtype), int(chunks), int(accumulate),
+                -1 if image_lanes is None else int(image_lanes), -1 if l2_warmup is None else int(l2_warmup),
+                what="msda_bordered_forward")
     return out
 
 
@@ -474,12 +463,10 @@ def msda_forward_head_major(value_hm: Tensor, spatial_shapes: Tensor, level_star
     B, M, Nv, D = value_hm.shape
     _, Nq, _, L, P, _ = sampling_loc.shape
     out = torch.empty((B, Nq, M * D), dtype=out_dtype, device=value_hm.device)
-    with torch.cuda.device(out.device):
-        code = _hip.lib(out_dtype).sdetr_msda_forward_head_major(
-            _hip.stream_ptr(), value_hm.data_ptr(), _hip.dtype_code(value_hm.dtype), spatial_shapes.data_ptr(),
-            level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-            B, Nv, M, D, L, Nq, P, out.data_ptr(), _hip.dtype_code(out_dtype))
-    _hip.check(code, "msda_forward_head_major")
+    _hip.launch("sdetr_msda_forward_head_major", out_dtype, out.device, value_hm.data_ptr(),
+                _hip.dtype_code(value_hm.dtype), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                sampling_loc.data_ptr(), attn_weight.data_ptr(), B, Nv, M, D, L, Nq, P, out.data_ptr(),
+                _hip.dtype_code(out_dtype))
     return out
 
 
@@ -613,11 +600,8 @@ class _SamplingPrep(Function):
         RD = ref.shape[-1]
         loc = torch.empty((B, Nq, M, L, P, 2), dtype=torch.float32, device=off.device)
         w = torch.empty((B, Nq, M, L, P), dtype=torch.float32, device=off.device)
-        with torch.cuda.device(off.device):
-            code = _hip.lib().sdetr_sampling_prep_f32(_hip.stream_ptr(), off.data_ptr(), lg.data_ptr(), ref.data_ptr(),
-                                                      spatial_shapes.data_ptr(), B * Nq, M, L, P, RD, loc.data_ptr(),
-                                                      w.data_ptr())
-        _hip.check(code, "sampling_prep")
+        _hip.launch("sdetr_sampling_prep_f32", None, off.device, off.data_ptr(), lg.data_ptr(), ref.data_ptr(),
+                    spatial_shapes.data_ptr(), B * Nq, M, L, P, RD, loc.data_ptr(), w.data_ptr(), what="sampling_prep")
         ctx.save_for_backward(w, ref, spatial_shapes)
         ctx.dims = (B, Nq, M, L, P, RD)
         return loc, w
@@ -630,11 +614,9 @@ class _SamplingPrep(Function):
         gl, gw = grad_loc.contiguous(), grad_w.contiguous()
         g_off = torch.empty((B, Nq, M, L, P, 2), dtype=torch.float32, device=w.device)
         g_lg = torch.empty((B, Nq, M, L * P), dtype=torch.float32, device=w.device)
-        with torch.cuda.device(w.device):
-            code = _hip.lib().sdetr_sampling_prep_backward_f32(
-                _hip.stream_ptr(), gl.data_ptr(), gw.data_ptr(), w.data_ptr(), ref.data_ptr(), spatial_shapes.data_ptr(),
-                B * Nq, M, L, P, RD, g_off.data_ptr(), g_lg.data_ptr())
-        _hip.check(code, "sampling_prep_backward")
+        _hip.launch("sdetr_sampling_prep_backward_f32", None, w.device, gl.data_ptr(), gw.data_ptr(), w.data_ptr(),
+                    ref.data_ptr(), spatial_shapes.data_ptr(), B * Nq, M, L, P, RD, g_off.data_ptr(), g_lg.data_ptr(),
+                    what="sampling_prep_backward")
         return g_off, g_lg, None, None, None, None
 
 

@@ -315,21 +315,17 @@ class ClippedAdamW(Optimizer):
 
     def _launch(self) -> None:
         t = self._tables
-        lib = _hip.lib()
-        stream = _hip.stream_ptr()
+        dev = t["records"].device
         g0 = self.param_groups[0]
-        _hip.check(lib.sdetr_adamw_grad_sumsq(stream, t["records"].data_ptr(), t["num_records"], t["chunks"].data_ptr(),
-                                              t["num_chunks"], t["wave_first"].data_ptr(), t["num_waves"],
-                                              t["num_partials"], self._partials.data_ptr(), self._counter.data_ptr()),
-                   "adamw_grad_sumsq", lib)
-        _hip.check(lib.sdetr_adamw_clip_step(stream, t["records"].data_ptr(), t["num_records"], t["chunks"].data_ptr(),
-                                             t["num_chunks"], t["wave_first"].data_ptr(), t["num_waves"],
-                                             t["num_partials"], self._partials.data_ptr(), self._counter.data_ptr(),
-                                             self._group_table.data_ptr(), len(self.param_groups),
-                                             self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
-                                             float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]),
-                                             self.max_norm, self.grad_scale, self._norm.data_ptr()),
-                   "adamw_clip_step", lib)
+        _hip.launch("sdetr_adamw_grad_sumsq", None, dev, t["records"].data_ptr(), t["num_records"],
+                    t["chunks"].data_ptr(), t["num_chunks"], t["wave_first"].data_ptr(), t["num_waves"],
+                    t["num_partials"], self._partials.data_ptr(), self._counter.data_ptr())
+        _hip.launch("sdetr_adamw_clip_step", None, dev, t["records"].data_ptr(), t["num_records"],
+                    t["chunks"].data_ptr(), t["num_chunks"], t["wave_first"].data_ptr(), t["num_waves"],
+                    t["num_partials"], self._partials.data_ptr(), self._counter.data_ptr(),
+                    self._group_table.data_ptr(), len(self.param_groups), self._exp_avg.data_ptr(),
+                    self._exp_avg_sq.data_ptr(), float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]),
+                    self.max_norm, self.grad_scale, self._norm.data_ptr())
 
     def _account(self, active: List[int]) -> None:
         """Host bookkeeping of a step that ran: step counts, and the version bump the raw-pointer write did not make."""

@@ -69,9 +69,7 @@ def level_masks_and_positions(mask: Tensor, level_shapes: Sequence[Tuple[int, in
     hw = (ctypes.c_int * (2 * n))(*[v for s in shapes for v in s])
     mptr = (ctypes.c_void_p * n)(*[m.data_ptr() for m in masks])
     pptr = (ctypes.c_void_p * n)(*[p.data_ptr() for p in pos])
-    lib = _hip.lib()
-    _hip.check(lib.sdetr_frontend_masks_positions(_hip.stream_ptr(), src.data_ptr(), B, H, W, n, hw, dty.data_ptr(),
-                                                  dtx.data_ptr(), F_, int(bool(pe.normalize)), float(pe.scale),
-                                                  float(pe.eps), float(pe.offset), mptr, pptr),
-               "level_masks_and_positions", lib)
+    _hip.launch("sdetr_frontend_masks_positions", None, src.device, src.data_ptr(), B, H, W, n, hw, dty.data_ptr(),
+                dtx.data_ptr(), F_, int(bool(pe.normalize)), float(pe.scale), float(pe.eps), float(pe.offset), mptr,
+                pptr, what="level_masks_and_positions")
     return masks, pos

@@ -88,13 +88,10 @@ def detections_padded(pred_logits: torch.Tensor, pred_boxes: torch.Tensor, targe
     if nms_iou_threshold > 0 and iou < float(np.finfo(np.float32).tiny):
         iou = float(np.finfo(np.float32).tiny)
     L = _hip.lib(pred_logits.dtype)
-    with torch.cuda.device(dev):
-        code = L.sdetr_detection_postprocess(
-            _hip.stream_ptr(), pred_logits.data_ptr(), _hip.dtype_code(pred_logits.dtype), logits_stride,
-            pred_boxes.data_ptr(), boxes_stride, target_sizes.data_ptr(),
-            _hip.I64 if target_sizes.dtype == torch.int64 else _hip.F32, B, Nq, C, int(k), thr, iou,
-            scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(), count.data_ptr())
-    _hip.check(code, "detection_postprocess", L)
+    _hip.launch("sdetr_detection_postprocess", L, dev, pred_logits.data_ptr(), _hip.dtype_code(pred_logits.dtype),
+                logits_stride, pred_boxes.data_ptr(), boxes_stride, target_sizes.data_ptr(),
+                _hip.I64 if target_sizes.dtype == torch.int64 else _hip.F32, B, Nq, C, int(k), thr, iou,
+                scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(), count.data_ptr())
     return scores, labels, boxes, count
 
 

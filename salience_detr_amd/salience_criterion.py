@@ -35,14 +35,12 @@ def salience_targets(boxes_xyxy: Tensor, box_offset: Tensor, level_shapes: Seque
     target = torch.empty((B, S), dtype=torch.float32, device=box_offset.device)
     if noise_scale and (noise is None or tuple(noise.shape) != (B, S) or noise.dtype != torch.float32):
         raise RuntimeError("salience_targets: noise_scale needs an fp32 noise tensor [B,S]")
-    with torch.cuda.device(target.device):
-        code = _hip.lib().sdetr_salience_targets(
-            _hip.stream_ptr(), boxes.data_ptr(), box_offset.data_ptr(), B,
-            _host_array(ctypes.c_int64, [(int(h), int(w)) for h, w in level_shapes]),
-            _host_array(ctypes.c_float, [(float(a), float(b)) for a, b in feature_strides]),
-            _host_array(ctypes.c_float, [(float(a), float(b)) for a, b in limit_range[:len(level_shapes)]]),
-            len(level_shapes), float(noise_scale), _hip.ptr(noise.contiguous() if noise_scale else None), target.data_ptr())
-    _hip.check(code, "salience_targets")
+    _hip.launch("sdetr_salience_targets", None, target.device, boxes.data_ptr(), box_offset.data_ptr(), B,
+                _host_array(ctypes.c_int64, [(int(h), int(w)) for h, w in level_shapes]),
+                _host_array(ctypes.c_float, [(float(a), float(b)) for a, b in feature_strides]),
+                _host_array(ctypes.c_float, [(float(a), float(b)) for a, b in limit_range[:len(level_shapes)]]),
+                len(level_shapes), float(noise_scale), _hip.ptr(noise.contiguous() if noise_scale else None),
+                target.data_ptr())
     return target
 
 
@@ -59,10 +57,8 @@ class _FocalLoss(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=x.device)
         ws_bytes = max(int(lib.sdetr_focal_loss_workspace_bytes(n)), 8)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            code = lib.sdetr_salience_focal_loss(_hip.stream_ptr(), x.data_ptr(), t.data_ptr(), n, float(alpha), float(gamma),
-                                                 float(positive_threshold), ws.data_ptr(), ws_bytes, out.data_ptr())
-        _hip.check(code, "salience_focal_loss")
+        _hip.launch("sdetr_salience_focal_loss", lib, x.device, x.data_ptr(), t.data_ptr(), n, float(alpha),
+                    float(gamma), float(positive_threshold), ws.data_ptr(), ws_bytes, out.data_ptr())
         ctx.save_for_backward(x, t, out)
         ctx.alpha, ctx.gamma, ctx.in_dtype = float(alpha), float(gamma), logits.dtype
         return out[0]
@@ -72,11 +68,8 @@ class _FocalLoss(torch.autograd.Function):
         x, t, out = ctx.saved_tensors
         grad = torch.empty_like(x)
         g = grad_loss.detach().float().reshape(1).contiguous()
-        with torch.cuda.device(x.device):
-            code = _hip.lib().sdetr_salience_focal_loss_backward(_hip.stream_ptr(), x.data_ptr(), t.data_ptr(), x.numel(),
-                                                                 ctx.alpha, ctx.gamma, out.data_ptr(), g.data_ptr(),
-                                                                 grad.data_ptr())
-        _hip.check(code, "salience_focal_loss_backward")
+        _hip.launch("sdetr_salience_focal_loss_backward", None, x.device, x.data_ptr(), t.data_ptr(), x.numel(),
+                    ctx.alpha, ctx.gamma, out.data_ptr(), g.data_ptr(), grad.data_ptr())
         return grad.to(ctx.in_dtype), None, None, None, None
 
 

@@ -169,13 +169,10 @@ def match_outputs(logits: Sequence[Tensor], boxes: Sequence[Tensor], staged: Sta
     match = torch.empty((P, Nq), dtype=torch.int32, device=dev)
     status = torch.empty((P,), dtype=torch.int32, device=dev)
     duals = torch.empty((P, Nq + staged.capacity), dtype=torch.float64, device=dev) if with_duals else None
-    with torch.cuda.device(dev):
-        code = L.sdetr_set_match(_hip.stream_ptr(), table, len(logits), _hip.dtype_code(logits[0].dtype), B, Nq, C,
-                                 staged.boxes.data_ptr(), staged.labels.data_ptr(), staged.offsets.data_ptr(),
-                                 staged.capacity, float(cost_class), float(cost_bbox), float(cost_giou),
-                                 float(focal_alpha), float(focal_gamma), 0, 0, ws.data_ptr(), ws_bytes,
-                                 match.data_ptr(), _hip.ptr(duals), status.data_ptr())
-    _hip.check(code, what, L)
+    _hip.launch("sdetr_set_match", L, dev, table, len(logits), _hip.dtype_code(logits[0].dtype), B, Nq, C,
+                staged.boxes.data_ptr(), staged.labels.data_ptr(), staged.offsets.data_ptr(), staged.capacity,
+                float(cost_class), float(cost_bbox), float(cost_giou), float(focal_alpha), float(focal_gamma), 0, 0,
+                ws.data_ptr(), ws_bytes, match.data_ptr(), _hip.ptr(duals), status.data_ptr(), what=what)
     del keep
     res = [match, status]
     if with_duals:
@@ -199,11 +196,9 @@ def dn_match(staged: StagedTargets, num_queries: int, denoising_groups: int, max
     L = _hip.lib()
     match = torch.empty((n_outputs * B, num_queries), dtype=torch.int32, device=dev)
     status = torch.empty((n_outputs * B,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        code = L.sdetr_set_match(_hip.stream_ptr(), None, n_outputs, _hip.F32, B, num_queries, 1, None, None,
-                                 staged.offsets.data_ptr(), 0, 0.0, 0.0, 0.0, 0.0, 0.0, int(denoising_groups),
-                                 int(max_gt_num_per_image), None, 0, match.data_ptr(), None, status.data_ptr())
-    _hip.check(code, "dn_match", L)
+    _hip.launch("sdetr_set_match", L, dev, None, n_outputs, _hip.F32, B, num_queries, 1, None, None,
+                staged.offsets.data_ptr(), 0, 0.0, 0.0, 0.0, 0.0, 0.0, int(denoising_groups), int(max_gt_num_per_image),
+                None, 0, match.data_ptr(), None, status.data_ptr(), what="dn_match")
     return match, status
 
 
@@ -232,12 +227,10 @@ class _SetLoss(torch.autograd.Function):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         losses = torch.empty((n, 3), dtype=torch.float32, device=dev)
         st = spec.staged
-        with torch.cuda.device(dev):
-            code = L.sdetr_set_loss(_hip.stream_ptr(), table, n, _hip.dtype_code(logits[0].dtype), B, Nq, C,
-                                    st.boxes.data_ptr(), st.labels.data_ptr(), st.offsets.data_ptr(), spec.match.data_ptr(),
-                                    _hip.ptr(spec.num_boxes), float(spec.num_boxes_scale), float(spec.alpha),
-                                    float(spec.gamma), ws.data_ptr(), ws_bytes, losses.data_ptr())
-        _hip.check(code, "set_loss", L)
+        _hip.launch("sdetr_set_loss", L, dev, table, n, _hip.dtype_code(logits[0].dtype), B, Nq, C, st.boxes.data_ptr(),
+                    st.labels.data_ptr(), st.offsets.data_ptr(), spec.match.data_ptr(), _hip.ptr(spec.num_boxes),
+                    float(spec.num_boxes_scale), float(spec.alpha), float(spec.gamma), ws.data_ptr(), ws_bytes,
+                    losses.data_ptr())
         del keep
         ctx.spec = spec
         ctx.save_for_backward(*tensors)
@@ -259,12 +252,10 @@ class _SetLoss(torch.autograd.Function):
         gl_ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in gl])
         gb_ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in gb])
         st = spec.staged
-        with torch.cuda.device(dev):
-            code = L.sdetr_set_loss_backward(_hip.stream_ptr(), table, n, _hip.dtype_code(logits[0].dtype), B, Nq, C,
-                                             st.boxes.data_ptr(), st.labels.data_ptr(), st.offsets.data_ptr(),
-                                             spec.match.data_ptr(), _hip.ptr(spec.num_boxes), float(spec.num_boxes_scale),
-                                             float(spec.alpha), float(spec.gamma), g.data_ptr(), gl_ptrs, gb_ptrs)
-        _hip.check(code, "set_loss_backward", L)
+        _hip.launch("sdetr_set_loss_backward", L, dev, table, n, _hip.dtype_code(logits[0].dtype), B, Nq, C,
+                    st.boxes.data_ptr(), st.labels.data_ptr(), st.offsets.data_ptr(), spec.match.data_ptr(),
+                    _hip.ptr(spec.num_boxes), float(spec.num_boxes_scale), float(spec.alpha), float(spec.gamma),
+                    g.data_ptr(), gl_ptrs, gb_ptrs)
         del keep
         grads = [None]
         for a, b in zip(gl, gb):
