@@ -1368,6 +1368,64 @@ int sdetr_backbone_bwd_run(sdetr_stream_t stream, const sdetr_backbone_bwd_op *o
                            void *workspace, int64_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * ConvNeXt backbone (models/backbones/convnext.py), eval mode, csrc/convnext.hip.
+ *
+ * The residual stream is channels-last f32 [batch, H, W, C] in BOTH precisions; `precision` (as for the ResNet: 0 = fp32
+ * accuracy by the exact three-way bf16 split, 1 = one 16-bit product with fp32 accumulation) sets the products and the
+ * "compute dtype" of the GEMM A operands written between launches (f32, or the library's 16-bit type).
+ *
+ * sdetr_convnext_op, by kind (height / width are always the op's INPUT size):
+ *   0 patchify GEMM, linear epilogue: x channels-last [batch, height, width, in_channels] in the compute dtype
+ *     (in_channels % 32 == 0), or with x_nchw the f32 NCHW canvas [batch, in_channels, height, width] (any in_channels);
+ *     a convolution with kernel_size == stride in 1 .. 4 and no padding, i.e. a GEMM over gathered patches (a Linear is
+ *     kernel 1 over rows, the down-sampler kernel 2, the stem kernel 4 with x_nchw).  weight / bias = sdetr_backbone_pack's
+ *     planes and bias (layout 0, or 1 with x_nchw; gamma = 1, mean = 0, var = 1, eps = 0 packs the weight as it is, and
+ *     gamma = layer_scale folds it: gamma (W h + b) = (gamma W) h + gamma b).  out f32 [batch, Ho, Wo, out_channels] =
+ *     acc + bias (+ residual, f32, shaped as out, or NULL); out_nchw (or NULL) the same values as f32 NCHW.
+ *   1 the same GEMM with out = gelu(acc + bias) (the exact erf form) in the compute dtype; no residual, no out_nchw.
+ *   2 depthwise 7x7 (padding 3, zeros) + bias + LayerNorm(eps) over C in one launch: x f32 [batch, height, width, C],
+ *     weight f32 [49][C] (tap-major: tap ky * 7 + kx of channel c at [ky * 7 + kx][c]), bias / gamma / beta f32 [C];
+ *     out [batch, height, width, C] in the compute dtype.  C = in_channels, a multiple of 32 up to 3072; accumulation
+ *     and statistics in f32.  sdetr_convnext_dw_tile: the tile the launch takes for C channels (8 x tile_height pixels,
+ *     channel chunk, strip width); returns the dynamic LDS bytes, or -1.
+ *   3 LayerNorm(eps) over C of f32 rows x [batch, height, width, C] (C % 32 == 0, up to 3072) with gamma / beta; out in
+ *     the compute dtype, or f32 when out_f32.
+ * splits (kinds 0 / 1): 0 = automatic, n > 0 = n pieces of the reduction (clamped), summed in a fixed order through the
+ * workspace (no atomics: bit-identical from run to run).  Every launch writes every element of its output.
+ * sdetr_convnext_op_run runs one op; sdetr_convnext_run a whole plan in order, validated before the first launch;
+ * the workspace must hold sdetr_convnext_workspace_bytes (the largest split buffer of the plan).  Tensors 16-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_convnext_op {
+    int kind;
+    const void *x;
+    const void *weight;
+    const float *bias;
+    const float *gamma;
+    const float *beta;
+    const float *residual;
+    void *out;
+    float *out_nchw;
+    int batch;
+    int in_channels;
+    int height;
+    int width;
+    int out_channels;
+    int kernel_size;
+    int stride;
+    int x_nchw;
+    int out_f32;
+    int splits;
+    float eps;
+} sdetr_convnext_op;
+
+int sdetr_convnext_dw_tile(int channels, int *tile_height, int *chunk_channels, int *strip_width);
+int64_t sdetr_convnext_workspace_bytes(const sdetr_convnext_op *ops, int n_ops, int precision);
+int sdetr_convnext_op_run(sdetr_stream_t stream, const sdetr_convnext_op *op, int precision, void *workspace,
+                          int64_t workspace_bytes);
+int sdetr_convnext_run(sdetr_stream_t stream, const sdetr_convnext_op *ops, int n_ops, int precision, void *workspace,
+                       int64_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.
  *
  * sdetr_cdn_queries: ONE launch.  boxes f32 [batch * capacity, 4] (cx, cy, w, h in [0, 1]), labels int32

@@ -2,7 +2,8 @@
 points are also reachable from the package, resolved on first use so that importing the package stays free of torch."""
 
 _LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "SalienceDETRHead": "detector",
-         "EvalResize": "eval_resize", "eval_resize_size": "eval_resize", "batch_images": "backbone"}
+         "EvalResize": "eval_resize", "eval_resize_size": "eval_resize", "batch_images": "backbone",
+         "ConvNeXtBackbone": "convnext", "CNBlockConfig": "convnext"}
 
 
 def __getattr__(name):

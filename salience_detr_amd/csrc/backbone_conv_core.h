@@ -1,0 +1,279 @@
+// The implicit-GEMM convolution kernel of the backbones, its operand loaders and its epilogues: shared by the ResNet
+// (backbone.hip: folded-BN convs, EPI 0) and the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
+// convs, EPI 1 / 2).  Tiles and the MFMA half step: backbone_core.h.
+#pragma once
+
+#include <algorithm>
+#include <type_traits>
+
+#include "backbone_core.h"
+#include "common.h"
+#include "gelu_core.h"
+
+namespace sdetr {
+namespace {
+
+struct BConv {
+    const char *x;          // NHWC compute dtype, or (nchw) the fp32 NCHW canvas
+    const uint16_t *w;      // packed [planes][co][kpad]
+    const float *bias;      // folded [co]
+    const char *res;        // NHWC [M][co] compute dtype, or null
+    char *out;              // NHWC [M][co] compute dtype
+    float *out_nchw;        // fp32 NCHW [B][co][Ho][Wo], or null
+    float *partial;         // split-K pieces [splits][M][co]
+    uint32_t x_bytes, w_bytes;
+    int batch, ci, h, w_in, co, ks, stride, pad, ho, wo, M, K, kpad, relu, splits, k_per_split;
+    int64_t plane;          // co * kpad
+};
+
+// where output pixel m reads its taps: input row / column of tap (0, 0) and the image's first element
+struct RowInfo {
+    int iy0, ix0, base;
+};
+__device__ __forceinline__ RowInfo row_info(const BConv &c, int m, int base_scale)
+{
+    RowInfo r;
+    if (m >= c.M) {
+        r.iy0 = -(1 << 28);   // every tap out of range: the row reads zeros
+        r.ix0 = 0;
+        r.base = 0;
+        return r;
+    }
+    const int hw = c.ho * c.wo, n = m / hw, rem = m - n * hw, oy = rem / c.wo, ox = rem - oy * c.wo;
+    r.iy0 = oy * c.stride - c.pad;
+    r.ix0 = ox * c.stride - c.pad;
+    r.base = n * base_scale;
+    return r;
+}
+
+// A tile, channels-last input (C % 32 == 0): one tap, 32 contiguous channels per pixel row; 16-byte pieces.
+// fp32: 8 pieces per row, rows tid / 8 + 64 j (j < 4); 16-bit: 4 pieces per row, rows tid / 4 + 128 j (j < 2).
+template <bool X3>
+struct ALoadNHWC {
+    static constexpr int kRows = X3 ? 4 : 2, kStep = X3 ? 64 : 128, kShift = X3 ? 3 : 2, kEsz = X3 ? 4 : 2;
+    RowInfo ri[kRows];
+    uint4 v[kRows];
+    __device__ __forceinline__ void init(const BConv &c, int m0, int tid)
+    {
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) ri[j] = row_info(c, m0 + (tid >> kShift) + kStep * j, c.h * c.w_in);
+    }
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t rs, int k0, int kend, int tid)
+    {
+        const int tap = k0 / c.ci, c0 = k0 - tap * c.ci, ky = tap / c.ks, kx = tap - ky * c.ks;
+        const uint32_t piece = 16u * (uint32_t)(tid & ((1 << kShift) - 1));
+        const bool kok = k0 < kend;
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            const int iy = ri[j].iy0 + ky, ix = ri[j].ix0 + kx;
+            const bool ok = kok && (unsigned)iy < (unsigned)c.h && (unsigned)ix < (unsigned)c.w_in;
+            const uint32_t pix = (uint32_t)ri[j].base + (uint32_t)iy * (uint32_t)c.w_in + (uint32_t)ix;   // (wraps when !ok)
+            v[j] = buffer_load16(rs, b_off(ok, (pix * (uint32_t)c.ci + (uint32_t)c0) * kEsz + piece));
+        }
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        constexpr int row = X3 ? kBRow32 : kBRow16;
+        char *d = tile + (tid >> kShift) * row + 16 * (tid & ((1 << kShift) - 1));
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) *reinterpret_cast<uint4 *>(d + kStep * j * row) = v[j];
+    }
+};
+
+// A tile, the stem: fp32 NCHW canvas, any channel count; 16 reduction indices of one pixel row per thread
+template <bool X3>
+struct ALoadNCHW {
+    RowInfo ri;
+    float v[16];
+    __device__ __forceinline__ void init(const BConv &c, int m0, int tid)
+    {
+        ri = row_info(c, m0 + (tid >> 1), c.ci * c.h * c.w_in);
+    }
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t, int k0, int kend, int tid)
+    {
+        const float *x = reinterpret_cast<const float *>(c.x);
+        const int kk2 = c.ks * c.ks, kb = k0 + 16 * (tid & 1), kmax = min(kend, c.K);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int k = kb + e, ci = k / kk2, t = k - ci * kk2, ky = t / c.ks, kx = t - ky * c.ks;
+            const int iy = ri.iy0 + ky, ix = ri.ix0 + kx;
+            const bool ok = k < kmax && (unsigned)iy < (unsigned)c.h && (unsigned)ix < (unsigned)c.w_in;
+            v[e] = ok ? x[ri.base + ((int64_t)ci * c.h + iy) * c.w_in + ix] : 0.f;
+        }
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        if (X3) {
+            char *d = tile + (tid >> 1) * kBRow32 + 64 * (tid & 1);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                *reinterpret_cast<float4 *>(d + 16 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        } else {
+            char *d = tile + (tid >> 1) * kBRow16 + 32 * (tid & 1);
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                *reinterpret_cast<uint4 *>(d + 16 * q) =
+                    make_uint4(pack_act2(v[8 * q], v[8 * q + 1]), pack_act2(v[8 * q + 2], v[8 * q + 3]),
+                               pack_act2(v[8 * q + 4], v[8 * q + 5]), pack_act2(v[8 * q + 6], v[8 * q + 7]));
+        }
+    }
+};
+
+// B tile: the packed weight, 128 output channels x 32 reduction indices per plane, 16 bytes per thread and plane
+template <int PL>
+struct BLoadW {
+    uint4 q[PL];
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t rs, int n0, int k0, int kend, int tid)
+    {
+        const int r = n0 + (tid >> 2), k = k0 + 8 * (tid & 3);
+        const bool ok = r < c.co && k < kend;
+        const uint32_t o = ((uint32_t)r * (uint32_t)c.kpad + (uint32_t)k) * 2u, plane = (uint32_t)(c.plane * 2);
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) q[pl] = buffer_load16(rs, b_off(ok, o + pl * plane));
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        char *d = tile + (tid >> 2) * kBRow16 + 16 * (tid & 3);
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) *reinterpret_cast<uint4 *>(d + pl * kBPlane) = q[pl];
+    }
+};
+
+// The epilogue of one output element, by EPI:
+//   0  relu?(v + b'[co] (+ residual)) -> out (NHWC, compute dtype) and the fp32 NCHW copy (the ResNet's)
+//   1  gelu(v + b[co]) -> out (rows, compute dtype): the first Linear of a ConvNeXt block (convnext.hip)
+//   2  v + b[co] (+ fp32 residual) -> out (fp32 rows, the ConvNeXt residual stream in every precision) and the NCHW copy
+template <bool X3, int EPI>
+__device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
+{
+    v += c.bias[co];
+    const int64_t e = (int64_t)m * c.co + co;
+    if (EPI == 1) {
+        v = gelu_erf(v);
+        if (X3) reinterpret_cast<float *>(c.out)[e] = v;
+        else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
+        return;
+    }
+    if (c.res) {
+        if (X3 || EPI == 2) v += reinterpret_cast<const float *>(c.res)[e];
+        else v += act_lo(reinterpret_cast<const uint16_t *>(c.res)[e]);
+    }
+    if (EPI == 0 && c.relu) v = fmaxf(v, 0.f);
+    if (X3 || EPI == 2) reinterpret_cast<float *>(c.out)[e] = v;
+    else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
+    if (c.out_nchw) {
+        const int hw = c.ho * c.wo, n = m / hw, pix = m - n * hw;
+        c.out_nchw[((int64_t)n * c.co + co) * hw + pix] = v;
+    }
+}
+
+template <bool X3, bool NCHW, int EPI>
+__global__ void __launch_bounds__(kBThreads, 1) backbone_conv_kernel(BConv c)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    using Cfg = BCfg<X3>;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.x * kBM, n0 = blockIdx.y * kBN;
+    const int kbeg = blockIdx.z * c.k_per_split, kend = min(c.kpad, kbeg + c.k_per_split);
+    const __amdgpu_buffer_rsrc_t rx = make_uniform_rsrc(c.x, c.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = make_uniform_rsrc(reinterpret_cast<const char *>(c.w), c.w_bytes);
+
+    b_f32x16_t acc[2][2];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[rt][ct][i] = 0.f;
+
+    typename std::conditional<NCHW, ALoadNCHW<X3>, ALoadNHWC<X3>>::type ta;
+    BLoadW<X3 ? 3 : 1> tb;
+    ta.init(c, m0, tid);
+    ta.load(c, rx, kbeg, kend, tid);
+    tb.load(c, rw, n0, kbeg, kend, tid);
+    ta.store(lds, tid);
+    tb.store(lds + Cfg::kA, tid);
+    __syncthreads();
+    const int fa = X3 ? (64 * wm + (lane & 31)) * kBRow32 + (lane >> 5) * 32 : (64 * wm + (lane & 31)) * kBRow16 + (lane >> 5) * 16;
+    const int fb = Cfg::kA + (64 * wn + (lane & 31)) * kBRow16 + (lane >> 5) * 16;
+    int cur = 0;
+    for (int k0 = kbeg; k0 < kend; k0 += kBK) {
+        const bool more = k0 + kBK < kend;   // (uniform)
+        if (more) {                          // the next tile travels in registers while this one is multiplied
+            ta.load(c, rx, k0 + kBK, kend, tid);
+            tb.load(c, rw, n0, k0 + kBK, kend, tid);
+        }
+        const char *s = lds + cur * Cfg::kStage;
+        half_step<X3>(s + fa, s + fb, 0, acc);
+        half_step<X3>(s + fa, s + fb, 1, acc);
+        if (more) {   // the other stage's last readers passed the previous barrier
+            char *d = lds + (cur ^ 1) * Cfg::kStage;
+            ta.store(d, tid);
+            tb.store(d + Cfg::kA, tid);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const int co = n0 + 64 * wn + 32 * ct + (lane & 31);
+        if (co >= c.co) continue;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int m = m0 + 64 * wm + 32 * rt + b_acc_row(i, lane);
+                if (m >= c.M) continue;
+                if (c.splits > 1) c.partial[((int64_t)blockIdx.z * c.M + m) * c.co + co] = acc[rt][ct][i];
+                else emit<X3, EPI>(c, m, co, acc[rt][ct][i]);
+            }
+    }
+}
+
+// the split-K pieces summed in split order (deterministic), then the epilogue
+template <bool X3, int EPI>
+__global__ void __launch_bounds__(256) backbone_splitk_kernel(BConv c)
+{
+    const int64_t total = (int64_t)c.M * c.co, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        float v = c.partial[e];
+        for (int z = 1; z < c.splits; ++z) v += c.partial[(int64_t)z * total + e];
+        const int m = (int)(e / c.co), co = (int)(e - (int64_t)m * c.co);
+        emit<X3, EPI>(c, m, co, v);
+    }
+}
+
+// ---- host: the split of the reduction and the launch (the conv kernel, then the fixed-order sum of its pieces)
+int out_hw(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+int round32(int v) { return (v + 31) / 32 * 32; }
+
+int resolve_splits(int M, int co, int kpad, int requested)
+{
+    const int steps = kpad / kBK;
+    if (requested > 0) return std::max(1, std::min(requested, steps));
+    const int tiles = ((M + kBM - 1) / kBM) * ((co + kBN - 1) / kBN);
+    if (tiles >= 192) return 1;
+    return std::max(1, std::min({8, 256 / tiles, steps / 4}));
+}
+
+int64_t conv_workspace(const BConv &c) { return c.splits > 1 ? (int64_t)c.splits * c.M * c.co * 4 : 0; }
+
+template <bool X3, bool NCHW, int EPI>
+void launch_conv(hipStream_t s, const BConv &c)
+{
+    static DeviceOnce once;
+    allow_dynamic_lds(backbone_conv_kernel<X3, NCHW, EPI>, once, BCfg<X3>::kLds);
+    const dim3 grid((unsigned)((c.M + kBM - 1) / kBM), (unsigned)((c.co + kBN - 1) / kBN), (unsigned)c.splits);
+    hipLaunchKernelGGL((backbone_conv_kernel<X3, NCHW, EPI>), grid, dim3(kBThreads), BCfg<X3>::kLds, s, c);
+    if (c.splits > 1) {
+        const int64_t total = (int64_t)c.M * c.co;
+        const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+        hipLaunchKernelGGL((backbone_splitk_kernel<X3, EPI>), dim3(blocks), dim3(256), 0, s, c);
+    }
+}
+
+}  // namespace
+}  // namespace sdetr
