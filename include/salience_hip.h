@@ -1426,6 +1426,83 @@ int sdetr_convnext_run(sdetr_stream_t stream, const sdetr_convnext_op *ops, int 
                        int64_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * FocalNet backbone (models/backbones/focalnet.py), eval mode, csrc/focalnet.hip.
+ *
+ * As for the ConvNeXt: the residual stream is channels-last f32 [batch, H, W, C] in BOTH precisions; `precision` 0 = fp32
+ * accuracy by the exact three-way bf16 split, 1 = one 16-bit product with fp32 accumulation and the GEMM A operands in the
+ * library's 16-bit type (the "compute dtype").  Depthwise work, gates, means, LayerNorm statistics and q are f32.
+ * "rows" are pixels m = (n * H + y) * W + x.  C = in_channels of kinds 3 .. 7: a multiple of 32 up to 3072.
+ *
+ * sdetr_focalnet_op, by kind (height / width are always the op's INPUT size):
+ *   0 convolution as an implicit GEMM, linear epilogue: x channels-last [batch, height, width, in_channels] in the compute
+ *     dtype (in_channels % 32 == 0), or with x_nchw the f32 NCHW canvas (any in_channels); kernel_size 1 .. 7, stride
+ *     1 .. 4, padding < kernel_size, zeros outside the input.  The OUTPUT size out_height x out_width is the op's own: at
+ *     least the convolution's floor size, and the last window must still start inside the input -- the reference pads the
+ *     input with zeros up to a multiple of its patch first, which only adds output rows / columns (ceil(H / patch)).  A
+ *     Linear is kernel 1, stride 1, padding 0 over rows.  weight / bias = sdetr_backbone_pack's planes and bias (layout 0,
+ *     or 1 with x_nchw; gamma folds a per-output scale).  out f32 [batch, Ho, Wo, out_channels] = acc + bias (+ residual,
+ *     f32, shaped as out, or NULL).
+ *   1 the same over channels-last x with out = gelu(acc + bias) (exact erf form) in the compute dtype; no residual.
+ *   2 the same with out = (acc + bias) * q[m * q_ld + co] (q f32, q_ld >= out_channels, q_ld % 4 == 0): out in the compute
+ *     dtype, or f32 with out_f32.  This is h of the focal modulation; q points at f's output rows.
+ *   3 focal level: ctx_l = gelu(depthwise k x k (x)), k = kernel_size in {3, 5, 7, 9}, zero padding k / 2, no bias.  x f32,
+ *     channel c of row m at x[m * x_ld + c] (x_ld >= C, x_ld % 4 == 0: f's output rows at column C, or the previous
+ *     ctx_l with x_ld = C); weight f32 [k * k][C] tap-major; q = the gate, q[m * q_ld] (f's rows at column 2 C + l).
+ *     out (or NULL) = ctx_l f32 [rows][C]; out2 = ctx_all f32 [rows][C]: = ctx_l * gate, or += with accumulate.  With
+ *     last the launch also writes the sums of ctx_l over each 8 x 16 pixel tile, [batch][tiles][C], to the workspace.
+ *     x must not alias out.
+ *   4 modulator finish, directly after the `last` level of the same shape (it reads that level's sums from the
+ *     workspace): the sums are added in tile order, g = gelu(sum / (height * width)) per image and channel (two
+ *     launches), out[m][c] = x[m][c] + g[n][c] * q[m * q_ld] in the compute dtype; x = ctx_all f32, q = the last gate.
+ *   5 LayerNorm(eps) over C of f32 rows x with gamma / beta, + residual (f32 rows, or NULL): out in the compute dtype,
+ *     or f32 with out_f32; out2 (or NULL; precision 1 only) receives the same values in the 16-bit type.
+ *   6 LayerNorm(eps) over C of f32 rows x -> out f32 NCHW [batch, C, height, width].
+ *   7 x f32 rows -> out in the 16-bit type (precision 1 only).
+ * splits (kinds 0 .. 2): 0 = automatic, n > 0 = n pieces of the reduction (clamped), summed in a fixed order through the
+ * workspace.  No atomics anywhere: bit-identical from run to run.  Every launch writes every element of its outputs.
+ * sdetr_focalnet_op_run runs one op; sdetr_focalnet_run a whole plan in order, validated before the first launch (a
+ * null pointer, C % 32 != 0, an unsupported kernel size, a precision outside {0, 1}, a misaligned pointer or a
+ * workspace below sdetr_focalnet_workspace_bytes -- the largest need of the plan -- is SDETR_EINVAL with a message in
+ * sdetr_last_error).  Tensors 16-byte aligned (the gate: 4).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_focalnet_op {
+    int kind;
+    const void *x;
+    const void *weight;
+    const float *bias;
+    const float *gamma;
+    const float *beta;
+    const float *residual;
+    const float *q;
+    void *out;
+    void *out2;
+    int batch;
+    int in_channels;
+    int height;
+    int width;
+    int out_channels;
+    int out_height;
+    int out_width;
+    int kernel_size;
+    int stride;
+    int padding;
+    int x_nchw;
+    int out_f32;
+    int x_ld;
+    int q_ld;
+    int accumulate;
+    int last;
+    int splits;
+    float eps;
+} sdetr_focalnet_op;
+
+int64_t sdetr_focalnet_workspace_bytes(const sdetr_focalnet_op *ops, int n_ops, int precision);
+int sdetr_focalnet_op_run(sdetr_stream_t stream, const sdetr_focalnet_op *op, int precision, void *workspace,
+                          int64_t workspace_bytes);
+int sdetr_focalnet_run(sdetr_stream_t stream, const sdetr_focalnet_op *ops, int n_ops, int precision, void *workspace,
+                       int64_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.
  *
  * sdetr_cdn_queries: ONE launch.  boxes f32 [batch * capacity, 4] (cx, cy, w, h in [0, 1]), labels int32

@@ -1,6 +1,7 @@
 // The implicit-GEMM convolution kernel of the backbones, its operand loaders and its epilogues: shared by the ResNet
-// (backbone.hip: folded-BN convs, EPI 0) and the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
-// convs, EPI 1 / 2).  Tiles and the MFMA half step: backbone_core.h.
+// (backbone.hip: folded-BN convs, EPI 0), the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
+// convs, EPI 1 / 2) and the FocalNet (focalnet.hip: its Linears, the overlapped patch embedding, and h with the
+// modulation product, EPI 3 / 4).  Tiles and the MFMA half step: backbone_core.h.
 #pragma once
 
 #include <algorithm>
@@ -24,6 +25,8 @@ struct BConv {
     uint32_t x_bytes, w_bytes;
     int batch, ci, h, w_in, co, ks, stride, pad, ho, wo, M, K, kpad, relu, splits, k_per_split;
     int64_t plane;          // co * kpad
+    const float *q;         // EPI 3 / 4: the fp32 multiplier rows, element (m, co) at q[m * ldq + co]
+    int ldq;
 };
 
 // where output pixel m reads its taps: input row / column of tap (0, 0) and the image's first element
@@ -143,6 +146,8 @@ struct BLoadW {
 //   0  relu?(v + b'[co] (+ residual)) -> out (NHWC, compute dtype) and the fp32 NCHW copy (the ResNet's)
 //   1  gelu(v + b[co]) -> out (rows, compute dtype): the first Linear of a ConvNeXt block (convnext.hip)
 //   2  v + b[co] (+ fp32 residual) -> out (fp32 rows, the ConvNeXt residual stream in every precision) and the NCHW copy
+//   3  (v + b[co]) * q[m][co] -> out (rows, compute dtype): FocalNet's h with the modulation product (focalnet.hip)
+//   4  the same product -> out (fp32 rows in every precision): h in front of the modulation's own LayerNorm
 template <bool X3, int EPI>
 __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
 {
@@ -151,6 +156,12 @@ __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
     if (EPI == 1) {
         v = gelu_erf(v);
         if (X3) reinterpret_cast<float *>(c.out)[e] = v;
+        else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
+        return;
+    }
+    if (EPI == 3 || EPI == 4) {
+        v *= c.q[(int64_t)m * c.ldq + co];
+        if (X3 || EPI == 4) reinterpret_cast<float *>(c.out)[e] = v;
         else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
         return;
     }
