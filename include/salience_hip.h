@@ -1503,6 +1503,80 @@ int sdetr_focalnet_run(sdetr_stream_t stream, const sdetr_focalnet_op *ops, int 
                        int64_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * Swin backbone, V1 (models/backbones/swin.py: SwinTransformerBlock, PatchMerging), eval mode, csrc/swin.hip.
+ *
+ * As for the ConvNeXt and the FocalNet: the residual stream is channels-last f32 [batch, H, W, C] in BOTH precisions;
+ * `precision` 0 = fp32 accuracy (the GEMMs by the exact three-way bf16 split, the attention products by f32 MFMA),
+ * 1 = one 16-bit product with fp32 accumulation and the GEMM A operands, the qkv rows and the attention rows in the
+ * library's 16-bit type (the "compute dtype").  LayerNorm and softmax statistics are f32.  "rows" are pixels
+ * m = (n * H + y) * W + x.
+ *
+ * sdetr_swin_op, by kind (height / width are always the op's INPUT size):
+ *   0 patchify GEMM, linear epilogue: x channels-last [batch, height, width, in_channels] in the compute dtype
+ *     (in_channels % 32 == 0), or with x_nchw the f32 NCHW canvas (any in_channels); kernel_size == stride in 1 .. 4, no
+ *     padding, floor output size (a Linear is kernel 1 over rows, the stem kernel 4 with x_nchw).  weight / bias =
+ *     sdetr_backbone_pack's planes and bias (layout 0, or 1 with x_nchw; a Linear without a bias packs zeros).  out f32
+ *     [batch, Ho, Wo, out_channels] = acc + bias (+ residual, f32, shaped as out, or NULL); out_nchw (or NULL) the same
+ *     values as f32 NCHW.
+ *   1 the same GEMM over rows with out = gelu(acc + bias) (exact erf form) in the compute dtype; no residual, no out_nchw.
+ *   2 the same GEMM over rows with out = acc + bias in the compute dtype (qkv); no residual, no out_nchw.
+ *   3 LayerNorm(eps) over C = in_channels (a multiple of 32 up to 3072) of f32 rows x with gamma / beta: out in the compute
+ *     dtype, or f32 with out_f32.
+ *   4 window attention.  x = the qkv rows [batch * height * width][3 C] in the compute dtype, q | k | v each head-major
+ *     with head dimension 32 (C = in_channels = 32 * heads); bias f32 [3 C] = the qkv bias (already inside x: it is what
+ *     a token of the zero padding carries); table f32 [heads][N][N], N = window * window, the relative position bias per
+ *     (head, query, key); window 7 or 12; shift in [0, window).  The map is padded to multiples of the window at the
+ *     bottom / right and a padded token has q = k = v = bias (rounded to the compute dtype): it is a live key of every
+ *     window it falls into, and its output is dropped.  Per axis the shift is 0 when window >= padded size; the window
+ *     grid lies on the map rolled by -shift, and with a shift left on either axis a (query, key) pair whose regions
+ *     differ gets -100 (regions per axis with shift s > 0 and padded size P, at rolled coordinate c: 0 if c < P - window,
+ *     1 if c < P - s, else 2; an axis without shift is one region).  out [batch * height * width][C] in the compute
+ *     dtype = softmax(q 32^-0.5 k^T + table (+ mask)) v, each row at its ORIGINAL pixel.  x must not alias out.
+ *   5 patch-merging gather + LayerNorm(eps) over 4 C: x f32 [batch, height, width, C] (C = in_channels, 4 C a multiple of
+ *     32 up to 3072), gamma / beta f32 [4 C]; out [batch, ceil(height / 2), ceil(width / 2), 4 C] in the compute dtype,
+ *     row (i, j) = LN([x(2i, 2j) | x(2i + 1, 2j) | x(2i, 2j + 1) | x(2i + 1, 2j + 1)]), pixels beyond an odd height / width
+ *     zeros that enter the statistics.
+ * splits (kinds 0 .. 2): 0 = automatic, n > 0 = n pieces of the reduction (clamped), summed in a fixed order through the
+ * workspace.  No atomics anywhere: bit-identical from run to run.  Every launch writes every element of its outputs.
+ * sdetr_swin_op_run runs one op; sdetr_swin_run a whole plan in order, validated before the first launch (a null
+ * pointer, C % 32 != 0, a head dimension other than 32, a window other than 7 / 12, a precision outside {0, 1}, a
+ * misaligned pointer or a workspace below sdetr_swin_workspace_bytes -- the largest need of the plan -- is SDETR_EINVAL
+ * with a message in sdetr_last_error).  Tensors 16-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_swin_op {
+    int kind;
+    const void *x;
+    const void *weight;
+    const float *bias;
+    const float *gamma;
+    const float *beta;
+    const float *residual;
+    const float *table;
+    void *out;
+    float *out_nchw;
+    int batch;
+    int in_channels;
+    int height;
+    int width;
+    int out_channels;
+    int kernel_size;
+    int stride;
+    int x_nchw;
+    int out_f32;
+    int window;
+    int shift;
+    int heads;
+    int splits;
+    float eps;
+} sdetr_swin_op;
+
+int64_t sdetr_swin_workspace_bytes(const sdetr_swin_op *ops, int n_ops, int precision);
+int sdetr_swin_op_run(sdetr_stream_t stream, const sdetr_swin_op *op, int precision, void *workspace,
+                      int64_t workspace_bytes);
+int sdetr_swin_run(sdetr_stream_t stream, const sdetr_swin_op *ops, int n_ops, int precision, void *workspace,
+                   int64_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.
  *
  * sdetr_cdn_queries: ONE launch.  boxes f32 [batch * capacity, 4] (cx, cy, w, h in [0, 1]), labels int32

@@ -3,7 +3,8 @@ points are also reachable from the package, resolved on first use so that import
 
 _LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "SalienceDETRHead": "detector",
          "EvalResize": "eval_resize", "eval_resize_size": "eval_resize", "batch_images": "backbone",
-         "ConvNeXtBackbone": "convnext", "CNBlockConfig": "convnext", "FocalNetBackbone": "focalnet"}
+         "ConvNeXtBackbone": "convnext", "CNBlockConfig": "convnext", "FocalNetBackbone": "focalnet",
+         "SwinBackbone": "swin"}
 
 
 def __getattr__(name):

@@ -1,7 +1,7 @@
 // The implicit-GEMM convolution kernel of the backbones, its operand loaders and its epilogues: shared by the ResNet
 // (backbone.hip: folded-BN convs, EPI 0), the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
 // convs, EPI 1 / 2) and the FocalNet (focalnet.hip: its Linears, the overlapped patch embedding, and h with the
-// modulation product, EPI 3 / 4).  Tiles and the MFMA half step: backbone_core.h.
+// modulation product, EPI 3 / 4) and the Swin (swin.hip: its Linears and the stem, EPI 1 / 2 / 5).  Tiles and the MFMA half step: backbone_core.h.
 #pragma once
 
 #include <algorithm>
@@ -148,6 +148,7 @@ struct BLoadW {
 //   2  v + b[co] (+ fp32 residual) -> out (fp32 rows, the ConvNeXt residual stream in every precision) and the NCHW copy
 //   3  (v + b[co]) * q[m][co] -> out (rows, compute dtype): FocalNet's h with the modulation product (focalnet.hip)
 //   4  the same product -> out (fp32 rows in every precision): h in front of the modulation's own LayerNorm
+//   5  v + b[co] -> out (rows, compute dtype): Swin's qkv (swin.hip)
 template <bool X3, int EPI>
 __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
 {
@@ -155,6 +156,11 @@ __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
     const int64_t e = (int64_t)m * c.co + co;
     if (EPI == 1) {
         v = gelu_erf(v);
+        if (X3) reinterpret_cast<float *>(c.out)[e] = v;
+        else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
+        return;
+    }
+    if (EPI == 5) {
         if (X3) reinterpret_cast<float *>(c.out)[e] = v;
         else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
         return;

@@ -1,0 +1,495 @@
+"""The Swin backbone, V1, in front of ``ChannelMapper`` (reference ``models/backbones/swin.py``): DESIGN.md §4 "Swin
+backbone".
+
+``SwinBackbone(arch, weights=None, return_indices=(0, 1, 2, 3), freeze_indices=(), **kwargs)`` has the reference's
+constructor, ``num_channels`` and state-dict keys: those of its ``nn.Sequential(feature_extractor, PostProcess)``, i.e.
+``0.features.0.{0,2}.*`` (stem conv and LayerNorm), ``0.features.{2i+1}.{j}.*`` (the blocks of stage ``i``: ``norm1``,
+``attn.relative_position_bias_table``, ``attn.relative_position_index`` -- an integer buffer --, ``attn.qkv``,
+``attn.proj``, ``norm2``, ``mlp.0``, ``mlp.3``) and ``0.features.{2i+2}.{reduction.weight,norm.*}`` (patch merging) for
+``i < max(return_indices)``; later stages are not held.  ``arch`` is one of ``ARCHS`` (``swin_t`` .. ``swin_l_384``) or
+``None`` with ``embed_dim`` / ``depths`` / ``num_heads`` / ``window_size`` in ``kwargs`` (which also override an arch's).
+The V2 names raise: cosine attention, ``cpb_mlp`` and ``PatchMergingV2`` are not built.  ``forward(x)`` returns
+``{"features.{2i+1}": map}`` for ``i in return_indices``: fp32 NCHW, the stage's stream as it is (the reference's
+``PostProcess`` only permutes).  ``weights`` is a state dict (optionally under ``"model"``) or a local file path, loaded
+non-strictly with shape filtering; nothing is ever downloaded.
+
+How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/swin.hip``, one plan, one
+``sdetr_swin_run`` call per forward.  The residual stream is channels-last fp32 in every mode:
+  * stem: the 4x4 stride-4 conv on the fp32 NCHW canvas as an implicit GEMM (floor output size, no padding), LayerNorm;
+  * a block is 7 launches: LayerNorm -> qkv (GEMM, rows in the compute dtype) -> window attention (one workgroup per
+    window and head; the padding to a window multiple, the cyclic shift and its reverse are index arithmetic, the tokens of
+    the padding carry the qkv bias) -> proj + residual -> LayerNorm -> fc1 + GELU -> fc2 + residual; the last fc2 of a
+    returned stage also writes the fp32 NCHW map;
+  * patch merging: the 2x2 gather + LayerNorm(4C) in one launch, then the ``reduction`` GEMM.
+``set_dtype(bfloat16 | float16)`` takes one 16-bit product with fp32 accumulation and 16-bit rows between launches;
+LayerNorm and softmax statistics and the stream stay fp32.  A call with grad enabled on something that requires grad
+takes the plain-torch composite, which is the autograd path; a Swin backward in HIP is out of scope.  Explicit arguments
+with a window other than 7 / 12 or a head dimension other than 32 run the composite too (``hip_form()`` is False).  A CPU
+tensor on the HIP form raises: the hot path has no CPU fallback.
+"""
+import os
+from functools import partial
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor, nn
+
+from . import _hip
+from .convnext import StochasticDepth
+from .derived import derived
+
+MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/swin.hip); the merging norm sees 4 C
+WINDOWS = (7, 12)
+HEAD_DIM = 32
+
+
+class Permute(nn.Module):
+    def __init__(self, dims: Sequence[int]):
+        super().__init__()
+        self.dims = tuple(dims)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return x.permute(*self.dims)
+
+
+def _axis_regions(padded: int, window: int, shift: int, device) -> Tensor:
+    """The mask region of every coordinate of a rolled axis: 0 below ``padded - window``, 1 below ``padded - shift``,
+    else 2; one region when the axis is not shifted."""
+    c = torch.arange(padded, device=device)
+    if shift == 0:
+        return torch.zeros_like(c)
+    return (c >= padded - window).long() + (c >= padded - shift).long()
+
+
+class ShiftedWindowAttention(nn.Module):
+    """Window attention with a relative position bias on ``[B, H, W, C]``: the map is zero-padded to multiples of the
+    window, rolled by ``-shift`` on every axis longer than one window, cut into windows; pairs of tokens from different
+    regions of the rolled map get -100."""
+
+    def __init__(self, dim: int, window_size: Sequence[int], shift_size: Sequence[int], num_heads: int,
+                 attention_dropout: float = 0.0, dropout: float = 0.0):
+        super().__init__()
+        if len(window_size) != 2 or len(shift_size) != 2:
+            raise ValueError("window_size and shift_size must be of length 2")
+        self.window_size, self.shift_size, self.num_heads = list(window_size), list(shift_size), num_heads
+        self.attention_dropout, self.dropout = attention_dropout, dropout
+        self.qkv = nn.Linear(dim, dim * 3)
+        self.proj = nn.Linear(dim, dim)
+        wh, ww = self.window_size
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * wh - 1) * (2 * ww - 1), num_heads))
+        nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
+        ys, xs = torch.meshgrid(torch.arange(wh), torch.arange(ww), indexing="ij")
+        dy = ys.reshape(-1, 1) - ys.reshape(1, -1) + wh - 1
+        dx = xs.reshape(-1, 1) - xs.reshape(1, -1) + ww - 1
+        self.register_buffer("relative_position_index", (dy * (2 * ww - 1) + dx).reshape(-1))
+
+    def position_bias(self) -> Tensor:
+        """``[heads, N, N]``: the table looked up per (query, key)."""
+        n = self.window_size[0] * self.window_size[1]
+        return self.relative_position_bias_table[self.relative_position_index].view(n, n, -1).permute(2, 0, 1).contiguous()
+
+    def forward(self, x: Tensor) -> Tensor:
+        b, h, w, c = x.shape
+        (wh, ww), heads = self.window_size, self.num_heads
+        ph, pw = -(-h // wh) * wh, -(-w // ww) * ww
+        x = F.pad(x, (0, 0, 0, pw - w, 0, ph - h))
+        sh = 0 if wh >= ph else self.shift_size[0]
+        sw = 0 if ww >= pw else self.shift_size[1]
+        rolled = sh + sw > 0
+        if rolled:
+            x = torch.roll(x, shifts=(-sh, -sw), dims=(1, 2))
+        nh, nw, n = ph // wh, pw // ww, wh * ww
+        tokens = x.view(b, nh, wh, nw, ww, c).permute(0, 1, 3, 2, 4, 5).reshape(b * nh * nw, n, c)
+        q, k, v = self.qkv(tokens).reshape(-1, n, 3, heads, c // heads).permute(2, 0, 3, 1, 4).unbind(0)
+        scores = (q * (c // heads) ** -0.5).matmul(k.transpose(-2, -1)) + self.position_bias().unsqueeze(0)
+        if rolled:
+            ids = 3 * _axis_regions(ph, wh, sh, x.device)[:, None] + _axis_regions(pw, ww, sw, x.device)[None, :]
+            ids = ids.view(nh, wh, nw, ww).permute(0, 2, 1, 3).reshape(nh * nw, n)
+            mask = torch.where(ids[:, None, :] != ids[:, :, None], -100.0, 0.0).to(scores.dtype)
+            scores = (scores.view(b, nh * nw, heads, n, n) + mask[None, :, None]).view(-1, heads, n, n)
+        p = F.dropout(F.softmax(scores, dim=-1), p=self.attention_dropout, training=self.training)
+        out = p.matmul(v).transpose(1, 2).reshape(-1, n, c)
+        out = F.dropout(self.proj(out), p=self.dropout, training=self.training)
+        out = out.view(b, nh, nw, wh, ww, c).permute(0, 1, 3, 2, 4, 5).reshape(b, ph, pw, c)
+        if rolled:
+            out = torch.roll(out, shifts=(sh, sw), dims=(1, 2))
+        return out[:, :h, :w, :].contiguous()
+
+
+class SwinTransformerBlock(nn.Module):
+    def __init__(self, dim: int, num_heads: int, window_size: Sequence[int], shift_size: Sequence[int], mlp_ratio: float,
+                 dropout: float, attention_dropout: float, stochastic_depth_prob: float, norm_layer):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.attn = ShiftedWindowAttention(dim, window_size, shift_size, num_heads, attention_dropout, dropout)
+        self.stochastic_depth = StochasticDepth(stochastic_depth_prob, "row")
+        self.norm2 = norm_layer(dim)
+        hidden = int(dim * mlp_ratio)
+        self.mlp = nn.Sequential(nn.Linear(dim, hidden), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden, dim),
+                                 nn.Dropout(dropout))
+        for m in self.mlp:
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_uniform_(m.weight)
+                nn.init.normal_(m.bias, std=1e-6)
+
+    def forward(self, x: Tensor) -> Tensor:
+        x = x + self.stochastic_depth(self.attn(self.norm1(x)))
+        return x + self.stochastic_depth(self.mlp(self.norm2(x)))
+
+
+class PatchMerging(nn.Module):
+    """``[.., H, W, C]`` -> ``[.., ceil(H / 2), ceil(W / 2), 2 C]``: the 2 x 2 neighbours side by side (row parity first),
+    zeros beyond an odd size, LayerNorm(4 C), a Linear without bias."""
+
+    def __init__(self, dim: int, norm_layer):
+        super().__init__()
+        self.dim = dim
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = norm_layer(4 * dim)
+
+    def forward(self, x: Tensor) -> Tensor:
+        h, w = x.shape[-3], x.shape[-2]
+        x = F.pad(x, (0, 0, 0, w % 2, 0, h % 2))
+        x = torch.cat([x[..., dy::2, dx::2, :] for dx in (0, 1) for dy in (0, 1)], -1)
+        return self.reduction(self.norm(x))
+
+
+class SwinTransformer(nn.Module):
+    """The reference's ``SwinTransformer`` as its feature extractor keeps it: ``features`` up to the last returned stage,
+    that one without its merging layer, no ``norm`` / ``head``.  The stochastic-depth probabilities count the blocks of
+    the WHOLE ``depths``, as the reference's do."""
+
+    def __init__(self, patch_size: Sequence[int], embed_dim: int, depths: Sequence[int], num_heads: Sequence[int],
+                 window_size: Sequence[int], mlp_ratio: float = 4.0, dropout: float = 0.0, attention_dropout: float = 0.0,
+                 stochastic_depth_prob: float = 0.1, norm_layer=None, num_stages: Optional[int] = None):
+        super().__init__()
+        norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-5)
+        num_stages = len(depths) if num_stages is None else num_stages
+        patch = tuple(patch_size)
+        layers: List[nn.Module] = [nn.Sequential(nn.Conv2d(3, embed_dim, kernel_size=patch, stride=patch),
+                                                 Permute([0, 2, 3, 1]), norm_layer(embed_dim))]
+        total, block_id = sum(depths), 0
+        for i in range(num_stages):
+            dim = embed_dim * 2 ** i
+            blocks = []
+            for j in range(depths[i]):
+                sd_prob = stochastic_depth_prob * float(block_id) / (total - 1) if total > 1 else 0.0
+                shift = [0 if j % 2 == 0 else w // 2 for w in window_size]
+                blocks.append(SwinTransformerBlock(dim, num_heads[i], list(window_size), shift, mlp_ratio, dropout,
+                                                   attention_dropout, sd_prob, norm_layer))
+                block_id += 1
+            layers.append(nn.Sequential(*blocks))
+            if i < num_stages - 1:
+                layers.append(PatchMerging(dim, norm_layer))
+        self.features = nn.Sequential(*layers)
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                nn.init.trunc_normal_(m.weight, std=0.02)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+
+class PostProcess(nn.Module):
+    """The reference's ``PostProcess``: channels-last maps to NCHW; no parameters."""
+
+    def forward(self, feats: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        return {k: v.permute(0, 3, 1, 2) for k, v in feats.items()}
+
+
+def _arch(embed_dim, depths, num_heads, window, sd):
+    return dict(patch_size=(4, 4), embed_dim=embed_dim, depths=depths, num_heads=num_heads, window_size=(window, window),
+                stochastic_depth_prob=sd)
+
+
+ARCHS = {
+    "swin_t": _arch(96, (2, 2, 6, 2), (3, 6, 12, 24), 7, 0.2),
+    "swin_s": _arch(96, (2, 2, 18, 2), (3, 6, 12, 24), 7, 0.3),
+    "swin_b": _arch(128, (2, 2, 18, 2), (4, 8, 16, 32), 7, 0.5),
+    "swin_l": _arch(192, (2, 2, 18, 2), (6, 12, 24, 48), 7, 0.2),
+    "swin_b_384": _arch(128, (2, 2, 18, 2), (4, 8, 16, 32), 12, 0.2),
+    "swin_l_384": _arch(192, (2, 2, 18, 2), (6, 12, 24, 48), 12, 0.2),
+}
+V2_ARCHS = ("swin_v2_t", "swin_v2_b")
+
+
+class SwinBackbone(nn.Module):
+    def __init__(self, arch: Optional[str], weights: Union[None, str, Dict[str, Tensor]] = None,
+                 return_indices: Tuple[int, ...] = (0, 1, 2, 3), freeze_indices: Tuple[int, ...] = (), **kwargs):
+        super().__init__()
+        if arch in V2_ARCHS:
+            raise ValueError(f"SwinBackbone: {arch} is a Swin V2 architecture (cosine attention, cpb_mlp, PatchMergingV2); "
+                             f"V2 is not built, only the V1 architectures {tuple(ARCHS)}")
+        if arch is not None and arch not in ARCHS:
+            raise ValueError(f"Expected architecture in {tuple(ARCHS)} but got {arch}")
+        config = dict(ARCHS[arch]) if arch is not None else {}
+        config.update({k: v for k, v in kwargs.items() if v is not None})
+        config.pop("url", None)
+        config.pop("num_classes", None)
+        for unbuilt in ("block", "downsample_layer"):
+            if config.pop(unbuilt, None) is not None:
+                raise ValueError(f"SwinBackbone: a custom {unbuilt} (Swin V2) is not built")
+        missing = [k for k in ("embed_dim", "depths", "num_heads", "window_size") if k not in config]
+        if missing:
+            raise ValueError(f"SwinBackbone: arch=None needs {', '.join(k + '=...' for k in missing)}")
+        config.setdefault("patch_size", (4, 4))
+        self.return_indices = tuple(return_indices)
+        depths = tuple(config["depths"])
+        if not self.return_indices or max(self.return_indices) >= len(depths) or min(self.return_indices) < 0:
+            raise ValueError(f"SwinBackbone: return_indices {self.return_indices} do not fit {len(depths)} stages")
+        self.num_stages = max(self.return_indices) + 1
+        self.config = dict(config)
+        self.num_channels = [config["embed_dim"] * 2 ** i for i in self.return_indices]
+        self.add_module("0", SwinTransformer(num_stages=self.num_stages, **config))
+        self.add_module("1", PostProcess())
+        self.compute_dtype = torch.float32
+        if weights is not None:
+            self.load_weights(weights)
+        features = self.body.features
+        if len(freeze_indices) > 0:
+            self._freeze(features[0])
+        for i in freeze_indices:
+            for idx in (2 * i + 1, 2 * i + 2):
+                if idx < len(features):
+                    self._freeze(features[idx])
+
+    @property
+    def body(self) -> SwinTransformer:
+        return self._modules["0"]
+
+    @staticmethod
+    def _freeze(module: nn.Module):
+        module.eval()
+        for p in module.parameters():
+            p.requires_grad = False
+
+    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
+        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
+        match are skipped.  A full ``SwinTransformer`` checkpoint (keys ``features.*``, ``norm.*``, ``head.*``) is taken
+        too: what the extractor does not keep is dropped.  Never downloads."""
+        if isinstance(weights, str):
+            if not os.path.exists(weights):
+                raise FileNotFoundError(f"SwinBackbone: no weight file at {weights} (nothing is downloaded)")
+            weights = torch.load(weights, map_location="cpu")
+        if "model" in weights and isinstance(weights["model"], dict):
+            weights = weights["model"]
+        own = self.state_dict()
+        if not any(k.startswith("0.") for k in weights):
+            weights = {"0." + k: v for k, v in weights.items()}
+        matched = {k: v for k, v in weights.items() if k not in own or own[k].shape == v.shape}
+        return self.load_state_dict(matched, strict=False)
+
+    def set_dtype(self, dtype: torch.dtype):
+        """Precision of the products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16`` (one
+        16-bit product, fp32 accumulation, 16-bit rows between launches; the residual stream stays fp32).  Outputs are
+        fp32."""
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"SwinBackbone.set_dtype: {dtype} is not float32 / bfloat16 / float16")
+        self.compute_dtype = dtype
+        return self
+
+    # ------------------------------------------------------------------------------------------ form checks
+    def _stages(self):
+        """``(i, blocks, merging or None)`` per held stage."""
+        features = self.body.features
+        for i in range(self.num_stages):
+            yield i, features[2 * i + 1], (features[2 * i + 2] if 2 * i + 2 < len(features) else None)
+
+    def hip_form(self) -> bool:
+        """True when every layer is one the HIP kernels serve: a square patch up to 4, widths (and MLP widths) that are
+        multiples of 32 with 4 C up to ``MAX_CHANNELS`` in front of a merging, square windows of 7 or 12 with one shift,
+        head dimension 32, ``nn.LayerNorm`` norms."""
+        stem = self.body.features[0]
+        k, s = stem[0].kernel_size, stem[0].stride
+        if k[0] != k[1] or k != s or k[0] > 4:
+            return False
+        norms = [stem[2]]
+        for _, blocks, merging in self._stages():
+            for blk in blocks:
+                at = blk.attn
+                c = at.qkv.in_features
+                if c % 32 or c > MAX_CHANNELS or blk.mlp[0].out_features % 32 or c != at.num_heads * HEAD_DIM:
+                    return False
+                if at.window_size[0] != at.window_size[1] or at.window_size[0] not in WINDOWS:
+                    return False
+                if at.shift_size[0] != at.shift_size[1] or not 0 <= at.shift_size[0] < at.window_size[0]:
+                    return False
+                norms += [blk.norm1, blk.norm2]
+            if merging is not None:
+                if 4 * merging.dim > MAX_CHANNELS:
+                    return False
+                norms.append(merging.norm)
+        return all(type(n) is nn.LayerNorm and len(n.normalized_shape) == 1 and n.elementwise_affine and n.bias is not None
+                   for n in norms)
+
+    def _needs_autograd(self, x: Tensor) -> bool:
+        if not torch.is_grad_enabled():
+            return False
+        return x.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    # ------------------------------------------------------------------------------------------ forward
+    def forward(self, x: Tensor) -> Dict[str, Tensor]:
+        if self._needs_autograd(x) or not self.hip_form():
+            return self.forward_torch(x)
+        return self.forward_hip(x)
+
+    def forward_torch(self, x: Tensor) -> Dict[str, Tensor]:
+        """The differentiable composite (the holder modules themselves) on the input's device."""
+        outs = {}
+        features = self.body.features
+        x = features[0](x)
+        for i, blocks, merging in self._stages():
+            x = blocks(x)
+            if i in self.return_indices:
+                outs[f"features.{2 * i + 1}"] = x
+            if merging is not None:
+                x = merging(x)
+        outs = self._modules["1"](outs)
+        return {f"features.{2 * i + 1}": outs[f"features.{2 * i + 1}"].contiguous() for i in self.return_indices}
+
+    def _precision(self) -> int:
+        return 0 if self.compute_dtype == torch.float32 else 1
+
+    def _lib(self):
+        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
+
+    def _packed(self, layer: nn.Module, layout: int = 0) -> Tuple[Tensor, Tensor]:
+        """``(packed weight, bias)`` of a conv or Linear for the implicit GEMM (``sdetr_backbone_pack`` with a unit norm);
+        a Linear without a bias gets zeros.  Built once per parameter version, precision and compute dtype."""
+        precision, lib = self._precision(), self._lib()
+        w = layer.weight
+        co, ci, k = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
+
+        def build():
+            dev = w.device
+            w32 = w.detach().to(torch.float32).reshape(co, ci, k, k).contiguous()
+            zeros, ones = torch.zeros(co, device=dev), torch.ones(co, device=dev)
+            beta = zeros if layer.bias is None else layer.bias.detach().to(torch.float32).contiguous()
+            nbytes = lib.sdetr_backbone_packed_bytes(co, ci, k, precision)
+            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=dev)
+            bias = torch.empty(co, dtype=torch.float32, device=dev)
+            _hip.launch("sdetr_backbone_pack", lib, dev, w32.data_ptr(), ones.data_ptr(), beta.data_ptr(), zeros.data_ptr(),
+                        ones.data_ptr(), 0.0, co, ci, k, layout, precision, packed.data_ptr(), bias.data_ptr(),
+                        what="SwinBackbone (pack)")
+            return packed, bias
+        return derived(layer, "swin_packed", (w, layer.bias), build, extra=(precision, self.compute_dtype, layout))
+
+    def _affine(self, norm: nn.LayerNorm) -> Tuple[Tensor, Tensor]:
+        def build():
+            return (norm.weight.detach().to(torch.float32).contiguous(), norm.bias.detach().to(torch.float32).contiguous())
+        return derived(norm, "swin_affine", (norm.weight, norm.bias), build)
+
+    def _attention_operands(self, attn: ShiftedWindowAttention) -> Tuple[Tensor, Tensor]:
+        """``(bias [heads, N, N], qkv bias [3 C])`` in fp32: the table expanded through the index buffer."""
+        def build():
+            with torch.no_grad():
+                table = attn.position_bias().to(torch.float32).contiguous()
+            return table, attn.qkv.bias.detach().to(torch.float32).contiguous()
+        sources = (attn.relative_position_bias_table, attn.relative_position_index, attn.qkv.bias)
+        return derived(attn, "swin_attention", sources, build)
+
+    def build_plan(self, x: Tensor, splits: int = 0):
+        """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
+        ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op.
+        The buffers of a stage are shared by its blocks (the launches of a plan run in order on one stream)."""
+        act = self.compute_dtype if self._precision() == 1 else torch.float32
+        dev, batch = x.device, x.shape[0]
+        ops: List[_hip.SwinOpStruct] = []
+        names: List[str] = []
+        keep: List[Tensor] = [x]
+        outputs: Dict[str, Tensor] = {}
+
+        def new(shape, dtype):
+            t = torch.empty(shape, device=dev, dtype=dtype)
+            keep.append(t)
+            return t
+
+        def op(name, kind, **kw):
+            f = dict(kind=kind, x=None, weight=None, bias=None, gamma=None, beta=None, residual=None, table=None, out=None,
+                     out_nchw=None, batch=batch, in_channels=0, height=1, width=1, out_channels=0, kernel_size=1, stride=1,
+                     x_nchw=0, out_f32=0, window=0, shift=0, heads=0, splits=splits, eps=0.0)
+            f.update(kw)
+            ops.append(_hip.SwinOpStruct(**f))
+            names.append(name)
+
+        def gemm(name, kind, layer, src, out, h, w, layout=0, residual=None, nchw=None):
+            packed, bias = self._packed(layer, layout)
+            keep.extend((packed, bias))
+            k = layer.kernel_size[0] if isinstance(layer, nn.Conv2d) else 1
+            op(name, kind, x=src.data_ptr(), weight=packed.data_ptr(), bias=bias.data_ptr(), residual=_hip.ptr(residual),
+               out=out.data_ptr(), out_nchw=_hip.ptr(nchw), in_channels=layer.weight.shape[1], height=h, width=w,
+               out_channels=bias.numel(), kernel_size=k, stride=k, x_nchw=layout)
+
+        def layer_norm(name, norm, src, out, h, w, c, out_f32=False):
+            gamma, beta = self._affine(norm)
+            keep.extend((gamma, beta))
+            op(name, 3, x=src.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=out.data_ptr(), in_channels=c,
+               height=h, width=w, out_channels=c, out_f32=1 if out_f32 else 0, eps=float(norm.eps))
+
+        stem = self.body.features[0]
+        patch, c = stem[0].kernel_size[0], stem[0].out_channels
+        h, w = x.shape[2] // patch, x.shape[3] // patch
+        if h < 1 or w < 1:
+            raise RuntimeError(f"SwinBackbone: a {x.shape[2]} x {x.shape[3]} input is smaller than one patch")
+        raw = new((batch, h, w, c), torch.float32)
+        gemm("0.features.0.0", 0, stem[0], x, raw, x.shape[2], x.shape[3], layout=1)
+        stream = new((batch, h, w, c), torch.float32)
+        layer_norm("0.features.0.2", stem[2], raw, stream, h, w, c, out_f32=True)
+        for i, blocks, merging in self._stages():
+            rows = (batch, h, w)
+            hidden = blocks[0].mlp[0].out_features
+            a_in = new(rows + (c,), act)                    # LayerNorm output: a GEMM A operand
+            qkv = new(rows + (3 * c,), act)
+            a_att = new(rows + (c,), act)
+            mid = new(rows + (hidden,), act)
+            for j, blk in enumerate(blocks):
+                prefix = f"0.features.{2 * i + 1}.{j}"
+                at = blk.attn
+                layer_norm(prefix + ".norm1", blk.norm1, stream, a_in, h, w, c)
+                gemm(prefix + ".attn.qkv", 2, at.qkv, a_in, qkv, h, w)
+                table, qkv_bias = self._attention_operands(at)
+                keep.extend((table, qkv_bias))
+                op(prefix + ".attn", 4, x=qkv.data_ptr(), bias=qkv_bias.data_ptr(), table=table.data_ptr(), out=a_att.data_ptr(),
+                   in_channels=c, height=h, width=w, out_channels=c, window=at.window_size[0], shift=at.shift_size[0],
+                   heads=at.num_heads)
+                gemm(prefix + ".attn.proj", 0, at.proj, a_att, stream, h, w, residual=stream)
+                layer_norm(prefix + ".norm2", blk.norm2, stream, a_in, h, w, c)
+                gemm(prefix + ".mlp.0", 1, blk.mlp[0], a_in, mid, h, w)
+                nchw = None
+                if j == len(blocks) - 1 and i in self.return_indices:
+                    nchw = outputs[f"features.{2 * i + 1}"] = new((batch, c, h, w), torch.float32)
+                gemm(prefix + ".mlp.3", 0, blk.mlp[3], mid, stream, h, w, residual=stream, nchw=nchw)
+            if merging is not None:
+                prefix = f"0.features.{2 * i + 2}"
+                ho, wo = (h + 1) // 2, (w + 1) // 2
+                gathered = new((batch, ho, wo, 4 * c), act)
+                gamma, beta = self._affine(merging.norm)
+                keep.extend((gamma, beta))
+                op(prefix + ".norm", 5, x=stream.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(),
+                   out=gathered.data_ptr(), in_channels=c, height=h, width=w, out_channels=4 * c, eps=float(merging.norm.eps))
+                stream = new((batch, ho, wo, 2 * c), torch.float32)
+                gemm(prefix + ".reduction", 0, merging.reduction, gathered, stream, ho, wo)
+                h, w, c = ho, wo, 2 * c
+        outputs = {f"features.{2 * i + 1}": outputs[f"features.{2 * i + 1}"] for i in self.return_indices}
+        return ops, outputs, keep, names
+
+    def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+        if x.dtype != torch.float32:
+            x = x.float()
+        _hip.require_device("SwinBackbone", x=x)
+        for t in self.parameters():
+            _hip.require_device("SwinBackbone", parameter=t.detach())
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"SwinBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
+        if not self.hip_form():
+            raise RuntimeError("SwinBackbone: this configuration has no HIP form (window 7 / 12, head dimension 32)")
+        ops, outputs, keep, _ = self.build_plan(x, splits)
+        lib, precision = self._lib(), self._precision()
+        arr = (_hip.SwinOpStruct * len(ops))(*ops)
+        ws_bytes = lib.sdetr_swin_workspace_bytes(arr, len(ops), precision)
+        if ws_bytes < 0:
+            _hip.check(-1, "SwinBackbone (workspace)", lib)
+        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
+        _hip.launch("sdetr_swin_run", lib, x.device, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
+                    what="SwinBackbone (run)")
+        return outputs
