@@ -39,6 +39,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _hip
+from .backbone_base import HipBackbone
 from .derived import derived
 
 
@@ -233,7 +234,7 @@ def plan_shapes(block, layers: Sequence[int], num_stages: int, height: int, widt
     return shapes
 
 
-class ResNetBackbone(nn.Module):
+class ResNetBackbone(HipBackbone):
     def __init__(self, arch: str, weights: Union[None, str, Dict[str, Tensor]] = None,
                  return_indices: Tuple[int, ...] = (0, 1, 2, 3), freeze_indices: Tuple[int, ...] = (), **kwargs):
         super().__init__()
@@ -261,12 +262,6 @@ class ResNetBackbone(nn.Module):
         for i in freeze_indices:
             self._freeze(getattr(self, f"layer{i + 1}"))
 
-    @staticmethod
-    def _freeze(module: nn.Module):
-        module.eval()
-        for p in module.parameters():
-            p.requires_grad = False
-
     def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
         """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
         match are skipped (``util.utils.load_state_dict`` of the reference).  Never downloads."""
@@ -283,14 +278,6 @@ class ResNetBackbone(nn.Module):
 
     def stages(self) -> List[nn.Sequential]:
         return [getattr(self, f"layer{i + 1}") for i in range(self.num_stages)]
-
-    def set_dtype(self, dtype: torch.dtype):
-        """Precision of the convolutions: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16``
-        (one 16-bit product, fp32 accumulation, 16-bit activations between layers).  The outputs stay fp32."""
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError(f"ResNetBackbone.set_dtype: {dtype} is not float32 / bfloat16 / float16")
-        self.compute_dtype = dtype
-        return self
 
     # ------------------------------------------------------------------------------------------ form checks
     def _convs(self):
@@ -314,11 +301,6 @@ class ResNetBackbone(nn.Module):
                               if name in ("bn1", "bn2", "bn3", "downsample.1")]
         return all(isinstance(m, FrozenBatchNorm2d) for m in norms)
 
-    def _needs_autograd(self, x: Tensor) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        return x.requires_grad or any(p.requires_grad for p in self.parameters())
-
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, x: Tensor) -> Dict[str, Tensor]:
         if self.train_form == "hip" and self._needs_autograd(x):
@@ -336,12 +318,6 @@ class ResNetBackbone(nn.Module):
             if i in self.return_indices:
                 outs[f"layer{i + 1}"] = x
         return outs
-
-    def _precision(self) -> int:
-        return 0 if self.compute_dtype == torch.float32 else 1
-
-    def _lib(self):
-        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
 
     def _packed(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d, layout: int) -> Tuple[Tensor, Tensor]:
         """``(packed weight, folded bias)`` of ``conv`` + ``bn`` (``sdetr_backbone_pack``), built once per parameter
@@ -429,14 +405,7 @@ class ResNetBackbone(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"ResNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
         ops, outputs, keep = self.build_plan(x, splits, acts)
-        lib, precision = self._lib(), self._precision()
-        arr = (_hip.BackboneOpStruct * len(ops))(*ops)
-        ws_bytes = lib.sdetr_backbone_workspace_bytes(arr, len(ops), precision)
-        if ws_bytes < 0:
-            _hip.check(-1, "ResNetBackbone (workspace)", lib)
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
-        _hip.launch("sdetr_backbone_run", lib, x.device, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
-                    what="ResNetBackbone (run)")
+        self._run_plan(_hip.BackboneOpStruct, "sdetr_backbone", ops, x.device)
         return outputs
 
     # ------------------------------------------------------------------------------------------ training in HIP

@@ -1,0 +1,187 @@
+"""What the four HIP backbones (``backbone.py``, ``convnext.py``, ``focalnet.py``, ``swin.py``) share: ``HipBackbone``,
+the module base with the precision switch, the torch / HIP dispatch, checkpoint loading, the operand packers and the
+launch of a plan; ``PlanBuilder``, the op list a ``build_plan`` fills; and the two parameter-free holder modules
+``Permute`` and ``StochasticDepth``."""
+import os
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import torch
+from torch import Tensor, nn
+
+from . import _hip
+from .derived import derived
+
+
+class Permute(nn.Module):
+    def __init__(self, dims: Sequence[int]):
+        super().__init__()
+        self.dims = list(dims)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return torch.permute(x, self.dims)
+
+
+class StochasticDepth(nn.Module):
+    """torchvision's ``StochasticDepth``: in training one Bernoulli(1 - p) per sample (``"row"``) or per batch
+    (``"batch"``), survivors divided by 1 - p; the identity with ``p == 0`` or in ``eval()``."""
+
+    def __init__(self, p: float, mode: str):
+        super().__init__()
+        if p < 0.0 or p > 1.0:
+            raise ValueError(f"drop probability has to be between 0 and 1, but got {p}")
+        if mode not in ("batch", "row"):
+            raise ValueError(f"mode has to be either 'batch' or 'row', but got {mode}")
+        self.p, self.mode = p, mode
+
+    def forward(self, x: Tensor) -> Tensor:
+        if not self.training or self.p == 0.0:
+            return x
+        survival = 1.0 - self.p
+        size = [x.shape[0]] + [1] * (x.ndim - 1) if self.mode == "row" else [1] * x.ndim
+        noise = torch.empty(size, dtype=x.dtype, device=x.device).bernoulli_(survival)
+        if survival > 0.0:
+            noise.div_(survival)
+        return x * noise
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(p={self.p}, mode={self.mode})"
+
+
+class PlanBuilder:
+    """The op list of one forward: ``ops`` (structs of ``struct_type``), ``names`` (one label per op), ``keep`` (every
+    tensor the ops point into) and ``outputs`` (the returned maps).  ``defaults`` are the fields every op of the plan
+    starts from (the batch, the splits ..); the struct's remaining fields start at zero / null."""
+
+    def __init__(self, struct_type, x: Tensor, **defaults):
+        self.struct_type, self.device, self.defaults = struct_type, x.device, defaults
+        self.ops: list = []
+        self.names: List[str] = []
+        self.keep: List[Tensor] = [x]
+        self.outputs: Dict[str, Tensor] = {}
+
+    def new(self, shape, dtype) -> Tensor:
+        t = torch.empty(shape, device=self.device, dtype=dtype)
+        self.keep.append(t)
+        return t
+
+    def op(self, name: str, kind: int, **fields):
+        self.ops.append(self.struct_type(kind=kind, **{**self.defaults, **fields}))
+        self.names.append(name)
+
+    def layer_norm(self, name: str, kind: int, affine: Tuple[Tensor, Tensor], eps: float, src: Tensor, out: Tensor, h: int,
+                   w: int, c: int, out_f32: bool = False, **fields):
+        """LayerNorm over the ``c`` channels of the fp32 rows ``src`` ``[batch, h, w, c]`` into ``out``."""
+        gamma, beta = affine
+        self.keep.extend((gamma, beta))
+        self.op(name, kind, x=src.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=out.data_ptr(), in_channels=c,
+                height=h, width=w, out_channels=c, out_f32=1 if out_f32 else 0, eps=float(eps), **fields)
+
+
+class HipBackbone(nn.Module):
+    """A backbone with a HIP inference form (``forward_hip``, one plan per forward) and a plain-torch composite
+    (``forward_torch``, the autograd path); a subclass gives both, ``hip_form()`` and ``compute_dtype``."""
+
+    @staticmethod
+    def _freeze(module: nn.Module):
+        module.eval()
+        for p in module.parameters():
+            p.requires_grad = False
+
+    def _remap_checkpoint_keys(self, weights: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """The checkpoint's entries under this module's own state-dict keys."""
+        return weights
+
+    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
+        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
+        match are skipped (``util.utils.load_state_dict`` of the reference).  Never downloads."""
+        if isinstance(weights, str):
+            if not os.path.exists(weights):
+                raise FileNotFoundError(f"{type(self).__name__}: no weight file at {weights} (nothing is downloaded)")
+            weights = torch.load(weights, map_location="cpu")
+        if "model" in weights and isinstance(weights["model"], dict):
+            weights = weights["model"]
+        own = self.state_dict()
+        weights = self._remap_checkpoint_keys(weights)
+        matched = {k: v for k, v in weights.items() if k not in own or own[k].shape == v.shape}
+        return self.load_state_dict(matched, strict=False)
+
+    def set_dtype(self, dtype: torch.dtype):
+        """Precision of the products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16`` (one
+        16-bit product, fp32 accumulation, 16-bit GEMM operands between launches).  Outputs are fp32."""
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"{type(self).__name__}.set_dtype: {dtype} is not float32 / bfloat16 / float16")
+        self.compute_dtype = dtype
+        return self
+
+    def _needs_autograd(self, x: Tensor) -> bool:
+        if not torch.is_grad_enabled():
+            return False
+        return x.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    def forward(self, x: Tensor) -> Dict[str, Tensor]:
+        if self._needs_autograd(x) or not self.hip_form():
+            return self.forward_torch(x)
+        return self.forward_hip(x)
+
+    def _precision(self) -> int:
+        return 0 if self.compute_dtype == torch.float32 else 1
+
+    def _lib(self):
+        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
+
+    def _packed(self, layer: nn.Module, layout: int = 0, scale: Union[None, float, Tensor] = None, scale_bias: bool = True,
+                pad_to: int = 1) -> Tuple[Tensor, Tensor]:
+        """``(packed weight, bias)`` of a conv or Linear for the implicit GEMM (``sdetr_backbone_pack`` with a unit norm):
+        ``scale`` (a layer scale, or a constant) folded into the weight and, with ``scale_bias``, the bias; a layer
+        without a bias gets zeros; the output width zero-padded to a multiple of ``pad_to``.  Built once per parameter
+        version, precision and compute dtype."""
+        precision, lib = self._precision(), self._lib()
+        w = layer.weight
+        co, ci, k = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
+        cop = -(-co // pad_to) * pad_to
+
+        def build():
+            dev = w.device
+            w32 = torch.zeros((cop, ci, k, k), dtype=torch.float32, device=dev)
+            w32[:co] = w.detach().to(torch.float32).reshape(co, ci, k, k)
+            b32 = torch.zeros(cop, dtype=torch.float32, device=dev)
+            if layer.bias is not None:
+                b32[:co] = layer.bias.detach().to(torch.float32)
+            gamma = torch.ones(cop, device=dev)
+            if isinstance(scale, Tensor):
+                gamma[:co] = scale.detach().to(torch.float32).reshape(co)
+            elif scale is not None:
+                gamma *= float(scale)
+            beta = (b32 * gamma if scale_bias else b32).contiguous()
+            zeros, ones = torch.zeros(cop, device=dev), torch.ones(cop, device=dev)
+            nbytes = lib.sdetr_backbone_packed_bytes(cop, ci, k, precision)
+            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=dev)
+            bias = torch.empty(cop, dtype=torch.float32, device=dev)
+            _hip.launch("sdetr_backbone_pack", lib, dev, w32.data_ptr(), gamma.data_ptr(), beta.data_ptr(), zeros.data_ptr(),
+                        ones.data_ptr(), 0.0, cop, ci, k, layout, precision, packed.data_ptr(), bias.data_ptr(),
+                        what=f"{type(self).__name__} (pack)")
+            return packed, bias
+        sources = (w, layer.bias) + ((scale,) if isinstance(scale, Tensor) else ())
+        fixed = None if isinstance(scale, Tensor) else scale
+        return derived(layer, "rows_packed", sources, build,
+                       extra=(precision, self.compute_dtype, layout, fixed, scale_bias, pad_to))
+
+    def _affine(self, norm: nn.LayerNorm, scale: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The LayerNorm's affine in fp32, a layer scale folded in: ``g * (w n + b) = (g w) n + g b``."""
+        def build():
+            w, b = norm.weight.detach().to(torch.float32), norm.bias.detach().to(torch.float32)
+            if scale is not None:
+                g = scale.detach().to(torch.float32)
+                w, b = w * g, b * g
+            return w.contiguous(), b.contiguous()
+        return derived(norm, "rows_affine", (norm.weight, norm.bias, scale), build)
+
+    def _run_plan(self, struct_type, c_prefix: str, ops: list, device) -> None:
+        """Launch ``ops`` in order: ``<c_prefix>_run`` over a workspace of ``<c_prefix>_workspace_bytes``."""
+        lib, precision, who = self._lib(), self._precision(), type(self).__name__
+        arr = (struct_type * len(ops))(*ops)
+        ws_bytes = getattr(lib, c_prefix + "_workspace_bytes")(arr, len(ops), precision)
+        if ws_bytes < 0:
+            _hip.check(-1, f"{who} (workspace)", lib)
+        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=device)
+        _hip.launch(c_prefix + "_run", lib, device, arr, len(ops), precision, ws.data_ptr(), ws_bytes, what=f"{who} (run)")

@@ -23,7 +23,6 @@ A call with grad enabled on something that requires grad takes the plain-torch c
 ``F.layer_norm``, ``F.linear``, ``F.gelu``, row-mode stochastic depth), which is the autograd path; ConvNeXt backward in
 HIP is out of scope.  A CPU tensor on the HIP form raises: the hot path has no CPU fallback.
 """
-import os
 from functools import partial
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -32,6 +31,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
+from .backbone_base import HipBackbone, Permute, PlanBuilder, StochasticDepth  # noqa: F401 (both modules re-exported)
 from .derived import derived
 
 
@@ -42,41 +42,6 @@ class LayerNorm2d(nn.LayerNorm):
         x = x.permute(0, 2, 3, 1)
         x = F.layer_norm(x, self.normalized_shape, self.weight, self.bias, self.eps)
         return x.permute(0, 3, 1, 2)
-
-
-class Permute(nn.Module):
-    def __init__(self, dims: Sequence[int]):
-        super().__init__()
-        self.dims = list(dims)
-
-    def forward(self, x: Tensor) -> Tensor:
-        return torch.permute(x, self.dims)
-
-
-class StochasticDepth(nn.Module):
-    """torchvision's ``StochasticDepth``: in training one Bernoulli(1 - p) per sample (``"row"``) or per batch
-    (``"batch"``), survivors divided by 1 - p; the identity with ``p == 0`` or in ``eval()``."""
-
-    def __init__(self, p: float, mode: str):
-        super().__init__()
-        if p < 0.0 or p > 1.0:
-            raise ValueError(f"drop probability has to be between 0 and 1, but got {p}")
-        if mode not in ("batch", "row"):
-            raise ValueError(f"mode has to be either 'batch' or 'row', but got {mode}")
-        self.p, self.mode = p, mode
-
-    def forward(self, x: Tensor) -> Tensor:
-        if not self.training or self.p == 0.0:
-            return x
-        survival = 1.0 - self.p
-        size = [x.shape[0]] + [1] * (x.ndim - 1) if self.mode == "row" else [1] * x.ndim
-        noise = torch.empty(size, dtype=x.dtype, device=x.device).bernoulli_(survival)
-        if survival > 0.0:
-            noise.div_(survival)
-        return x * noise
-
-    def __repr__(self) -> str:
-        return f"{self.__class__.__name__}(p={self.p}, mode={self.mode})"
 
 
 class CNBlock(nn.Module):
@@ -176,7 +141,7 @@ ARCHS = {
 MAX_CHANNELS = 3072   # the depthwise + LayerNorm tile (csrc/convnext.hip)
 
 
-class ConvNeXtBackbone(nn.Module):
+class ConvNeXtBackbone(HipBackbone):
     def __init__(self, arch: Optional[str], weights: Union[None, str, Dict[str, Tensor]] = None,
                  return_indices: Tuple[int, ...] = (0, 1, 2, 3), freeze_indices: Tuple[int, ...] = (), **kwargs):
         super().__init__()
@@ -206,35 +171,8 @@ class ConvNeXtBackbone(nn.Module):
             if 2 * i + 2 < len(self.features):
                 self._freeze(self.features[2 * i + 2])
 
-    @staticmethod
-    def _freeze(module: nn.Module):
-        module.eval()
-        for p in module.parameters():
-            p.requires_grad = False
-
-    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
-        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
-        match are skipped (``util.utils.load_state_dict`` of the reference).  Never downloads."""
-        if isinstance(weights, str):
-            if not os.path.exists(weights):
-                raise FileNotFoundError(f"ConvNeXtBackbone: no weight file at {weights} (nothing is downloaded)")
-            weights = torch.load(weights, map_location="cpu")
-        if "model" in weights and isinstance(weights["model"], dict):
-            weights = weights["model"]
-        own = self.state_dict()
-        matched = {k: v for k, v in weights.items() if k not in own or own[k].shape == v.shape}
-        return self.load_state_dict(matched, strict=False)
-
     def stages(self) -> List[nn.Sequential]:
         return [self.features[2 * i + 1] for i in range(self.num_stages)]
-
-    def set_dtype(self, dtype: torch.dtype):
-        """Precision of the products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16`` (one
-        16-bit product, fp32 accumulation, 16-bit GEMM operands; the residual stream stays fp32).  Outputs are fp32."""
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError(f"ConvNeXtBackbone.set_dtype: {dtype} is not float32 / bfloat16 / float16")
-        self.compute_dtype = dtype
-        return self
 
     # ------------------------------------------------------------------------------------------ form checks
     def hip_form(self) -> bool:
@@ -250,17 +188,6 @@ class ConvNeXtBackbone(nn.Module):
         norms = [self.features[0][1]] + [self.features[2 * i + 2][0] for i in range(self.num_stages - 1)]
         return all(type(m) is LayerNorm2d for m in norms)
 
-    def _needs_autograd(self, x: Tensor) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        return x.requires_grad or any(p.requires_grad for p in self.parameters())
-
-    # ------------------------------------------------------------------------------------------ forward
-    def forward(self, x: Tensor) -> Dict[str, Tensor]:
-        if self._needs_autograd(x) or not self.hip_form():
-            return self.forward_torch(x)
-        return self.forward_hip(x)
-
     def forward_torch(self, x: Tensor) -> Dict[str, Tensor]:
         """The differentiable composite (the holder modules themselves) on the input's device."""
         outs = {}
@@ -270,36 +197,6 @@ class ConvNeXtBackbone(nn.Module):
                 outs[f"features.{idx}"] = x
         return outs
 
-    def _precision(self) -> int:
-        return 0 if self.compute_dtype == torch.float32 else 1
-
-    def _lib(self):
-        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
-
-    def _packed(self, layer: nn.Module, scale: Optional[Tensor], layout: int) -> Tuple[Tensor, Tensor]:
-        """``(packed weight, bias)`` of a conv or Linear as a patchify GEMM (``sdetr_backbone_pack`` with a unit norm),
-        ``scale`` (``layer_scale``) folded into both: built once per parameter version, precision and compute dtype."""
-        precision, lib = self._precision(), self._lib()
-        w = layer.weight
-        co, ci, k = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
-
-        def build():
-            dev = w.device
-            w32 = w.detach().to(torch.float32).contiguous()
-            b32 = layer.bias.detach().to(torch.float32)
-            gamma = torch.ones(co, device=dev) if scale is None else scale.detach().to(torch.float32).reshape(co).contiguous()
-            beta = (b32 * gamma).contiguous()
-            zeros, ones = torch.zeros(co, device=dev), torch.ones(co, device=dev)
-            nbytes = lib.sdetr_backbone_packed_bytes(co, ci, k, precision)
-            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=dev)
-            bias = torch.empty(co, dtype=torch.float32, device=dev)
-            _hip.launch("sdetr_backbone_pack", lib, dev, w32.data_ptr(), gamma.data_ptr(), beta.data_ptr(), zeros.data_ptr(),
-                        ones.data_ptr(), 0.0, co, ci, k, layout, precision, packed.data_ptr(), bias.data_ptr(),
-                        what="ConvNeXtBackbone (pack)")
-            return packed, bias
-        sources = (w, layer.bias) if scale is None else (w, layer.bias, scale)
-        return derived(layer, "convnext_packed", sources, build, extra=(precision, self.compute_dtype, layout))
-
     def _taps(self, conv: nn.Conv2d) -> Tuple[Tensor, Tensor]:
         """The depthwise taps tap-major ``[49, C]`` and the bias, fp32."""
         def build():
@@ -308,45 +205,27 @@ class ConvNeXtBackbone(nn.Module):
                     conv.bias.detach().to(torch.float32).contiguous())
         return derived(conv, "convnext_taps", (conv.weight, conv.bias), build)
 
-    def _affine(self, norm: nn.LayerNorm) -> Tuple[Tensor, Tensor]:
-        def build():
-            return (norm.weight.detach().to(torch.float32).contiguous(), norm.bias.detach().to(torch.float32).contiguous())
-        return derived(norm, "convnext_affine", (norm.weight, norm.bias), build)
-
     def build_plan(self, x: Tensor, splits: int = 0):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
         ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op."""
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
-        dev, batch = x.device, x.shape[0]
-        ops: List[_hip.ConvnextOpStruct] = []
-        names: List[str] = []
-        keep: List[Tensor] = [x]
-        outputs: Dict[str, Tensor] = {}
-
-        def new(shape, dtype):
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
+        batch = x.shape[0]
+        pb = PlanBuilder(_hip.ConvnextOpStruct, x, batch=batch, kernel_size=1, stride=1)
+        new, keep, outputs = pb.new, pb.keep, pb.outputs
 
         def gemm(name, kind, layer, src, h, w, ci, k, scale=None, residual=None, nchw=None, x_nchw=False):
-            packed, bias = self._packed(layer, scale, 1 if x_nchw else 0)
+            packed, bias = self._packed(layer, 1 if x_nchw else 0, scale)
             keep.extend((packed, bias))
             co, ho, wo = layer.weight.shape[0], (h - k) // k + 1, (w - k) // k + 1
             out = new((batch, ho, wo, co), act if kind == 1 else torch.float32)
-            ops.append(_hip.ConvnextOpStruct(kind, src.data_ptr(), packed.data_ptr(), bias.data_ptr(), None, None,
-                                             _hip.ptr(residual), out.data_ptr(), _hip.ptr(nchw), batch, ci, h, w, co, k, k,
-                                             1 if x_nchw else 0, 0, splits, 0.0))
-            names.append(name)
+            pb.op(name, kind, x=src.data_ptr(), weight=packed.data_ptr(), bias=bias.data_ptr(), residual=_hip.ptr(residual),
+                  out=out.data_ptr(), out_nchw=_hip.ptr(nchw), in_channels=ci, height=h, width=w, out_channels=co,
+                  kernel_size=k, stride=k, x_nchw=1 if x_nchw else 0, splits=splits)
             return out, ho, wo
 
         def layer_norm(name, norm, src, h, w, c, out_f32):
-            gamma, beta = self._affine(norm)
-            keep.extend((gamma, beta))
             out = new((batch, h, w, c), torch.float32 if out_f32 else act)
-            ops.append(_hip.ConvnextOpStruct(3, src.data_ptr(), None, None, gamma.data_ptr(), beta.data_ptr(), None,
-                                             out.data_ptr(), None, batch, c, h, w, c, 1, 1, 0, 1 if out_f32 else 0, 0,
-                                             float(norm.eps)))
-            names.append(name)
+            pb.layer_norm(name, 3, self._affine(norm), norm.eps, src, out, h, w, c, out_f32)
             return out
 
         h, w = x.shape[2], x.shape[3]
@@ -362,10 +241,9 @@ class ConvNeXtBackbone(nn.Module):
                 gamma, beta = self._affine(norm)
                 keep.extend((taps, dw_bias, gamma, beta))
                 rows = new((batch, h, w, c), act)
-                ops.append(_hip.ConvnextOpStruct(2, y.data_ptr(), taps.data_ptr(), dw_bias.data_ptr(), gamma.data_ptr(),
-                                                 beta.data_ptr(), None, rows.data_ptr(), None, batch, c, h, w, c, 7, 1, 0, 0, 0,
-                                                 float(norm.eps)))
-                names.append(prefix + ".block.0+2")
+                pb.op(prefix + ".block.0+2", 2, x=y.data_ptr(), weight=taps.data_ptr(), bias=dw_bias.data_ptr(),
+                      gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=rows.data_ptr(), in_channels=c, height=h, width=w,
+                      out_channels=c, kernel_size=7, eps=float(norm.eps))
                 hidden, _, _ = gemm(prefix + ".block.3", 1, fc1, rows, h, w, c, 1)
                 nchw = None
                 if i in self.return_indices and j == len(stage) - 1:
@@ -378,7 +256,7 @@ class ConvNeXtBackbone(nn.Module):
                 t = layer_norm(f"features.{2 * i + 2}.0", down[0], y, h, w, c, False)
                 y, h, w = gemm(f"features.{2 * i + 2}.1", 0, down[1], t, h, w, c, 2)
                 c = down[1].weight.shape[0]
-        return ops, outputs, keep, names
+        return pb.ops, outputs, keep, pb.names
 
     def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
         if x.dtype != torch.float32:
@@ -391,12 +269,5 @@ class ConvNeXtBackbone(nn.Module):
         if min(x.shape[2], x.shape[3]) < 4 * 2 ** (self.num_stages - 1):
             raise RuntimeError(f"ConvNeXtBackbone: a {tuple(x.shape[2:])} canvas leaves a stage without pixels")
         ops, outputs, keep, _ = self.build_plan(x, splits)
-        lib, precision = self._lib(), self._precision()
-        arr = (_hip.ConvnextOpStruct * len(ops))(*ops)
-        ws_bytes = lib.sdetr_convnext_workspace_bytes(arr, len(ops), precision)
-        if ws_bytes < 0:
-            _hip.check(-1, "ConvNeXtBackbone (workspace)", lib)
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
-        _hip.launch("sdetr_convnext_run", lib, x.device, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
-                    what="ConvNeXtBackbone (run)")
+        self._run_plan(_hip.ConvnextOpStruct, "sdetr_convnext", ops, x.device)
         return outputs

@@ -156,44 +156,15 @@ int make_conv(const char *what, const sdetr_backbone_op &o, int precision, BConv
         return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
     if ((reinterpret_cast<uintptr_t>(o.x) | reinterpret_cast<uintptr_t>(o.weight)) & 15)
         return fail("%s: x and weight must be 16-byte aligned", what);
-    c.x = reinterpret_cast<const char *>(o.x);
-    c.w = reinterpret_cast<const uint16_t *>(o.weight);
-    c.bias = o.bias;
-    c.res = reinterpret_cast<const char *>(o.residual);
-    c.out = reinterpret_cast<char *>(o.out);
+    const int ho = out_hw(o.height, o.kernel_size, o.stride, o.padding), wo = out_hw(o.width, o.kernel_size, o.stride, o.padding);
+    if (ho < 1 || wo < 1) return fail("%s: empty output", what);
+    const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
+                        o.kernel_size, o.stride, o.padding, ho, wo, o.x_nchw, o.splits};
+    if (int rc = fill_conv(what, g, precision, c)) return rc;
     c.out_nchw = o.out_nchw;
-    c.partial = nullptr;
-    c.batch = o.batch;
-    c.ci = o.in_channels;
-    c.h = o.height;
-    c.w_in = o.width;
-    c.co = o.out_channels;
-    c.ks = o.kernel_size;
-    c.stride = o.stride;
-    c.pad = o.padding;
-    c.ho = out_hw(o.height, o.kernel_size, o.stride, o.padding);
-    c.wo = out_hw(o.width, o.kernel_size, o.stride, o.padding);
-    if (c.ho < 1 || c.wo < 1) return fail("%s: empty output", what);
     c.relu = o.relu ? 1 : 0;
-    c.K = o.in_channels * o.kernel_size * o.kernel_size;
-    c.kpad = round32(c.K);
-    const int64_t M = (int64_t)o.batch * c.ho * c.wo;
-    const int64_t esz = (o.x_nchw || precision == 0) ? 4 : 2;
-    const int64_t x_bytes = (int64_t)o.batch * o.in_channels * o.height * o.width * esz;
-    const int64_t w_bytes = (int64_t)(precision == 0 ? 3 : 1) * o.out_channels * c.kpad * 2;
-    if (M >= (1 << 30) || x_bytes >= (int64_t(1) << 31) || w_bytes >= (int64_t(1) << 31) ||
-        M * o.out_channels >= (int64_t(1) << 31))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    c.M = (int)M;
-    c.x_bytes = (uint32_t)x_bytes;
-    c.w_bytes = (uint32_t)w_bytes;
-    c.plane = (int64_t)o.out_channels * c.kpad;
-    c.splits = resolve_splits(c.M, c.co, c.kpad, o.splits);
-    c.k_per_split = (c.kpad / kBK + c.splits - 1) / c.splits * kBK;
-    c.splits = (c.kpad + c.k_per_split - 1) / c.k_per_split;
     return 0;
 }
-
 
 int run_conv(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws, int64_t ws_bytes)
 {

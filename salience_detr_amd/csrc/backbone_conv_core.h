@@ -1,7 +1,10 @@
-// The implicit-GEMM convolution kernel of the backbones, its operand loaders and its epilogues: shared by the ResNet
-// (backbone.hip: folded-BN convs, EPI 0), the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
-// convs, EPI 1 / 2) and the FocalNet (focalnet.hip: its Linears, the overlapped patch embedding, and h with the
-// modulation product, EPI 3 / 4) and the Swin (swin.hip: its Linears and the stem, EPI 1 / 2 / 5).  Tiles and the MFMA half step: backbone_core.h.
+// The implicit-GEMM convolution kernel of the backbones, its operand loaders, its epilogues and the host side every family
+// shares (fill_conv: a validated geometry as the kernel's arguments; the split of the reduction; the launch).  Used by the
+// ResNet (backbone.hip: folded-BN convs, EPI 0), the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
+// convs, EPI 1 / 2), the FocalNet (focalnet.hip: its Linears, the overlapped patch embedding, and h with the modulation
+// product, EPI 3 / 4) and the Swin (swin.hip: its Linears and the stem, EPI 1 / 2 / 5).  What the three row-stream families
+// share beyond it (row LayerNorm, host checks, plan entry points): backbone_rows_core.h.  Tiles and the MFMA half step:
+// backbone_core.h.
 #pragma once
 
 #include <algorithm>
@@ -274,6 +277,54 @@ int resolve_splits(int M, int co, int kpad, int requested)
     const int tiles = ((M + kBM - 1) / kBM) * ((co + kBN - 1) / kBN);
     if (tiles >= 192) return 1;
     return std::max(1, std::min({8, 256 / tiles, steps / 4}));
+}
+
+// The geometry of one conv op, already checked against its family's rules: the tensors, the input [batch, h, w, ci] (or with
+// x_nchw the fp32 NCHW canvas), the kernel, and the op's own output size.
+struct ConvGeom {
+    const void *x, *weight;
+    const float *bias;
+    const void *residual;
+    void *out;
+    int batch, ci, h, w, co, ks, stride, pad, ho, wo, x_nchw, splits;
+};
+
+// c = the kernel's arguments for g: every member set (those a family adds afterwards -- out_nchw, q / ldq, relu -- start
+// null / 0), K padded to whole reduction tiles, the 32-bit size limits, the resolved split of the reduction
+int fill_conv(const char *what, const ConvGeom &g, int precision, BConv &c)
+{
+    c = BConv{};
+    c.x = reinterpret_cast<const char *>(g.x);
+    c.w = reinterpret_cast<const uint16_t *>(g.weight);
+    c.bias = g.bias;
+    c.res = reinterpret_cast<const char *>(g.residual);
+    c.out = reinterpret_cast<char *>(g.out);
+    c.batch = g.batch;
+    c.ci = g.ci;
+    c.h = g.h;
+    c.w_in = g.w;
+    c.co = g.co;
+    c.ks = g.ks;
+    c.stride = g.stride;
+    c.pad = g.pad;
+    c.ho = g.ho;
+    c.wo = g.wo;
+    c.K = g.ci * g.ks * g.ks;
+    c.kpad = round32(c.K);
+    const int64_t M = (int64_t)g.batch * g.ho * g.wo;
+    const int64_t esz = (g.x_nchw || precision == 0) ? 4 : 2;
+    const int64_t x_bytes = (int64_t)g.batch * g.ci * g.h * g.w * esz;
+    const int64_t w_bytes = (int64_t)(precision == 0 ? 3 : 1) * g.co * c.kpad * 2;
+    if (M >= (1 << 30) || x_bytes >= (int64_t(1) << 31) || w_bytes >= (int64_t(1) << 31) || M * g.co >= (int64_t(1) << 31))
+        return fail("%s: tensors too large for 32-bit offsets", what);
+    c.M = (int)M;
+    c.x_bytes = (uint32_t)x_bytes;
+    c.w_bytes = (uint32_t)w_bytes;
+    c.plane = (int64_t)g.co * c.kpad;
+    c.splits = resolve_splits(c.M, c.co, c.kpad, g.splits);
+    c.k_per_split = (c.kpad / kBK + c.splits - 1) / c.splits * kBK;
+    c.splits = (c.kpad + c.k_per_split - 1) / c.k_per_split;
+    return 0;
 }
 
 int64_t conv_workspace(const BConv &c) { return c.splits > 1 ? (int64_t)c.splits * c.M * c.co * 4 : 0; }

@@ -8,14 +8,15 @@
 //                               a lane's strip of SW pixels sliding over the staged row; the pre-norm values of the whole
 //                               tile stay in LDS (fp32), the statistics are two-pass sums over them (one wave per pixel),
 //                               the normalised rows leave in the compute dtype.  TH, CC and SW follow C (tile_for).
-//   convnext_ln_kernel          LayerNorm over C of fp32 rows (the stem's LayerNorm2d and the one in front of each
-//                               down-sampler): one wave per row, the row held in registers, fp32 or compute-dtype output
+//   ln_rows_kernel              LayerNorm over C of fp32 rows (the stem's LayerNorm2d and the one in front of each
+//                               down-sampler): backbone_rows_core.h's, fp32 or compute-dtype output
 //   the GEMMs                   backbone_conv_core.h's implicit-GEMM kernel with kernel == stride, padding 0: a Linear is
 //                               its 1x1 case over rows, the down-sampler its 2x2 stride-2 case, the stem its 4x4 stride-4
 //                               case on the fp32 NCHW canvas; epilogue gelu(acc + b) (EPI 1) or acc + b (+ fp32 residual)
 //                               with the fp32 NCHW copy of a returned stage (EPI 2).  Weights: sdetr_backbone_pack.
+// The row LayerNorm, the host checks of a rows op and the plan entry points are backbone_rows_core.h's.
 // No atomics; a split reduction is summed in split order through the workspace.
-#include "backbone_conv_core.h"
+#include "backbone_rows_core.h"
 
 namespace sdetr {
 namespace {
@@ -59,13 +60,6 @@ struct CnDw {
     int batch, h, w, c, th, cc, tiles_x, tiles_y;
     float eps;
 };
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <int SW, bool F32OUT>
 __global__ void __launch_bounds__(kCnThreads) convnext_dwconv_ln_kernel(CnDw a)
@@ -162,70 +156,15 @@ __global__ void __launch_bounds__(kCnThreads) convnext_dwconv_ln_kernel(CnDw a)
     }
 }
 
-// LayerNorm over C of fp32 rows [rows][C]; one wave per row, up to kCnMaxC / 256 quads per lane in registers
-template <bool F32OUT>
-__global__ void __launch_bounds__(kCnThreads) convnext_ln_kernel(const float *x, const float *gamma, const float *beta,
-                                                                 int64_t rows, int c, float eps, char *out)
-{
-    constexpr int kQ = kCnMaxC / 256;
-    const int lane = threadIdx.x & 63, nq = c >> 2;
-    const float inv_c = 1.f / (float)c;
-    const int64_t stride = (int64_t)gridDim.x * (kCnThreads / 64);
-    for (int64_t r = (int64_t)blockIdx.x * (kCnThreads / 64) + (threadIdx.x >> 6); r < rows; r += stride) {
-        const float *row = x + r * c;
-        float4 v[kQ];
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < kQ; ++i) {
-            const int q = lane + 64 * i;
-            v[i] = q < nq ? *reinterpret_cast<const float4 *>(row + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
-        const float mean = wave_sum(s) * inv_c;
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < kQ; ++i) {
-            if (lane + 64 * i >= nq) continue;
-            const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-            ss += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-        }
-        const float rstd = 1.f / sqrtf(wave_sum(ss) * inv_c + eps);
-#pragma unroll
-        for (int i = 0; i < kQ; ++i) {
-            const int q = lane + 64 * i;
-            if (q >= nq) continue;
-            const float4 g = *reinterpret_cast<const float4 *>(gamma + 4 * q);
-            const float4 be = *reinterpret_cast<const float4 *>(beta + 4 * q);
-            const float o0 = fmaf((v[i].x - mean) * rstd, g.x, be.x), o1 = fmaf((v[i].y - mean) * rstd, g.y, be.y);
-            const float o2 = fmaf((v[i].z - mean) * rstd, g.z, be.z), o3 = fmaf((v[i].w - mean) * rstd, g.w, be.w);
-            if (F32OUT) *reinterpret_cast<float4 *>(out + (r * c + 4 * q) * 4) = make_float4(o0, o1, o2, o3);
-            else *reinterpret_cast<uint2 *>(out + (r * c + 4 * q) * 2) = make_uint2(pack_act2(o0, o1), pack_act2(o2, o3));
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------ host
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int check_shape(const char *what, const sdetr_convnext_op &o, int precision)
-{
-    if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
-    if (o.batch < 1 || o.height < 1 || o.width < 1 || o.in_channels < 1)
-        return fail("%s: bad shape (batch %d, %d x %d, channels %d)", what, o.batch, o.height, o.width, o.in_channels);
-    if ((int64_t)o.batch * o.height * o.width * o.in_channels >= (int64_t(1) << 29))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    return 0;
-}
-
 int make_dw(const sdetr_convnext_op &o, int precision, CnDw &a, CnTile &t)
 {
     const char *what = "sdetr_convnext (depthwise + LayerNorm)";
-    if (int rc = check_shape(what, o, precision)) return rc;
+    if (int rc = check_rows_shape(what, o.batch, o.height, o.width, o.in_channels, precision)) return rc;
     if (!o.x || !o.weight || !o.bias || !o.gamma || !o.beta || !o.out) return fail("%s: null tensor", what);
     if (!tile_for(o.in_channels, t))
         return fail("%s: channels must be a multiple of 32 in [32, %d] (got %d)", what, kCnMaxC, o.in_channels);
-    if (!aligned16(o.x) || !aligned16(o.weight) || !aligned16(o.bias) || !aligned16(o.gamma) || !aligned16(o.beta) ||
-        !aligned16(o.out))
+    if (!all_aligned16(o.x, o.weight, o.bias, o.gamma, o.beta, o.out))
         return fail("%s: tensors must be 16-byte aligned", what);
     a.x = reinterpret_cast<const float *>(o.x);
     a.taps = reinterpret_cast<const float *>(o.weight);
@@ -275,28 +214,15 @@ int run_dw(hipStream_t s, const sdetr_convnext_op &o, int precision)
 
 int check_ln(const sdetr_convnext_op &o, int precision)
 {
-    const char *what = "sdetr_convnext (LayerNorm)";
-    if (int rc = check_shape(what, o, precision)) return rc;
-    if (!o.x || !o.gamma || !o.beta || !o.out) return fail("%s: null tensor", what);
-    if (o.in_channels % 32 || o.in_channels > kCnMaxC)
-        return fail("%s: channels must be a multiple of 32 up to %d (got %d)", what, kCnMaxC, o.in_channels);
-    if (!aligned16(o.x) || !aligned16(o.gamma) || !aligned16(o.beta) || !aligned16(o.out))
-        return fail("%s: tensors must be 16-byte aligned", what);
-    return 0;
+    return check_ln_rows("sdetr_convnext (LayerNorm)", o.batch, o.height, o.width, o.in_channels, precision, o.x, o.gamma, o.beta,
+                         o.out);
 }
 
 int run_ln(hipStream_t s, const sdetr_convnext_op &o, int precision)
 {
     if (int rc = check_ln(o, precision)) return rc;
-    const int64_t rows = (int64_t)o.batch * o.height * o.width;
-    const unsigned blocks = (unsigned)std::min<int64_t>((rows + 3) / 4, 16384);
-    const float *x = reinterpret_cast<const float *>(o.x);
-    if (precision == 0 || o.out_f32)
-        hipLaunchKernelGGL(convnext_ln_kernel<true>, dim3(blocks), dim3(kCnThreads), 0, s, x, o.gamma, o.beta, rows,
-                           o.in_channels, o.eps, reinterpret_cast<char *>(o.out));
-    else
-        hipLaunchKernelGGL(convnext_ln_kernel<false>, dim3(blocks), dim3(kCnThreads), 0, s, x, o.gamma, o.beta, rows,
-                           o.in_channels, o.eps, reinterpret_cast<char *>(o.out));
+    launch_ln_rows(s, precision == 0 || o.out_f32, o.x, o.gamma, o.beta, nullptr, (int64_t)o.batch * o.height * o.width,
+                   o.in_channels, o.eps, o.out, nullptr);
     return check_launch("sdetr_convnext (LayerNorm)");
 }
 
@@ -304,7 +230,7 @@ int run_ln(hipStream_t s, const sdetr_convnext_op &o, int precision)
 int make_gemm(const sdetr_convnext_op &o, int precision, BConv &c)
 {
     const char *what = "sdetr_convnext (patchify GEMM)";
-    if (int rc = check_shape(what, o, precision)) return rc;
+    if (int rc = check_rows_shape(what, o.batch, o.height, o.width, o.in_channels, precision)) return rc;
     if (!o.x || !o.weight || !o.bias || !o.out) return fail("%s: null tensor", what);
     if (o.out_channels < 1) return fail("%s: bad out_channels %d", what, o.out_channels);
     if (o.kernel_size < 1 || o.kernel_size > 4 || o.stride != o.kernel_size)
@@ -313,52 +239,14 @@ int make_gemm(const sdetr_convnext_op &o, int precision, BConv &c)
     if (o.x_nchw == 0 && o.in_channels % 32)
         return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
     if (o.kind == 1 && (o.residual || o.out_nchw)) return fail("%s: the GELU epilogue takes no residual / NCHW copy", what);
-    if (!aligned16(o.x) || !aligned16(o.weight)) return fail("%s: x and weight must be 16-byte aligned", what);
-    c.x = reinterpret_cast<const char *>(o.x);
-    c.w = reinterpret_cast<const uint16_t *>(o.weight);
-    c.bias = o.bias;
-    c.res = reinterpret_cast<const char *>(o.residual);
-    c.out = reinterpret_cast<char *>(o.out);
+    if (!all_aligned16(o.x, o.weight)) return fail("%s: x and weight must be 16-byte aligned", what);
+    const int ho = out_hw(o.height, o.kernel_size, o.stride, 0), wo = out_hw(o.width, o.kernel_size, o.stride, 0);
+    if (ho < 1 || wo < 1) return fail("%s: empty output", what);
+    const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
+                        o.kernel_size, o.stride, 0, ho, wo, o.x_nchw, o.splits};
+    if (int rc = fill_conv(what, g, precision, c)) return rc;
     c.out_nchw = o.out_nchw;
-    c.partial = nullptr;
-    c.batch = o.batch;
-    c.ci = o.in_channels;
-    c.h = o.height;
-    c.w_in = o.width;
-    c.co = o.out_channels;
-    c.ks = o.kernel_size;
-    c.stride = o.stride;
-    c.pad = 0;
-    c.ho = out_hw(o.height, o.kernel_size, o.stride, 0);
-    c.wo = out_hw(o.width, o.kernel_size, o.stride, 0);
-    if (c.ho < 1 || c.wo < 1) return fail("%s: empty output", what);
-    c.relu = 0;
-    c.K = o.in_channels * o.kernel_size * o.kernel_size;
-    c.kpad = round32(c.K);
-    const int64_t M = (int64_t)o.batch * c.ho * c.wo;
-    const int64_t esz = (o.x_nchw || precision == 0) ? 4 : 2;
-    const int64_t x_bytes = (int64_t)o.batch * o.in_channels * o.height * o.width * esz;
-    const int64_t w_bytes = (int64_t)(precision == 0 ? 3 : 1) * o.out_channels * c.kpad * 2;
-    if (M >= (1 << 30) || x_bytes >= (int64_t(1) << 31) || w_bytes >= (int64_t(1) << 31) ||
-        M * o.out_channels >= (int64_t(1) << 31))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    c.M = (int)M;
-    c.x_bytes = (uint32_t)x_bytes;
-    c.w_bytes = (uint32_t)w_bytes;
-    c.plane = (int64_t)o.out_channels * c.kpad;
-    c.splits = resolve_splits(c.M, c.co, c.kpad, o.splits);
-    c.k_per_split = (c.kpad / kBK + c.splits - 1) / c.splits * kBK;
-    c.splits = (c.kpad + c.k_per_split - 1) / c.k_per_split;
     return 0;
-}
-
-template <int EPI>
-void launch_gemm(hipStream_t s, const BConv &c, bool x3, bool nchw)
-{
-    if (x3 && nchw) launch_conv<true, true, EPI>(s, c);
-    else if (x3) launch_conv<true, false, EPI>(s, c);
-    else if (nchw) launch_conv<false, true, EPI>(s, c);
-    else launch_conv<false, false, EPI>(s, c);
 }
 
 int run_gemm(hipStream_t s, const sdetr_convnext_op &o, int precision, void *ws, int64_t ws_bytes)
@@ -417,36 +305,21 @@ extern "C" int sdetr_convnext_dw_tile(int channels, int *tile_height, int *chunk
     return t.lds;
 }
 
+using ConvnextPlan = Plan<sdetr_convnext_op, check_op, run_op>;
+
 extern "C" int64_t sdetr_convnext_workspace_bytes(const sdetr_convnext_op *ops, int n_ops, int precision)
 {
-    if (!ops || n_ops < 1) return -1;
-    int64_t most = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        int64_t need;
-        if (check_op(ops[i], precision, need)) return -1;
-        most = std::max(most, need);
-    }
-    return most;
+    return ConvnextPlan::workspace_bytes(ops, n_ops, precision);
 }
 
 extern "C" int sdetr_convnext_op_run(sdetr_stream_t stream, const sdetr_convnext_op *op, int precision, void *workspace,
                                      int64_t workspace_bytes)
 {
-    if (!op) return fail("sdetr_convnext_op_run: null op");
-    return run_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
+    return ConvnextPlan::op_run("sdetr_convnext", stream, op, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_convnext_run(sdetr_stream_t stream, const sdetr_convnext_op *ops, int n_ops, int precision,
                                   void *workspace, int64_t workspace_bytes)
 {
-    if (!ops || n_ops < 1) return fail("sdetr_convnext_run: empty plan");
-    for (int i = 0; i < n_ops; ++i) {   // validate the whole plan before the first launch
-        int64_t need;
-        if (check_op(ops[i], precision, need)) return SDETR_EINVAL;
-        if (need > workspace_bytes || (need && !workspace))
-            return fail("sdetr_convnext_run: op %d needs %lld workspace bytes", i, (long long)need);
-    }
-    for (int i = 0; i < n_ops; ++i)
-        if (int rc = run_op((hipStream_t)stream, ops[i], precision, workspace, workspace_bytes)) return rc;
-    return 0;
+    return ConvnextPlan::run("sdetr_convnext", stream, ops, n_ops, precision, workspace, workspace_bytes);
 }

@@ -12,11 +12,14 @@
 //                             level also leaves the tile's per-channel sums of ctx_L in the workspace
 //   focal_mean_kernel         the tile sums added in tile order: gelu(mean over H x W) per image and channel
 //   focal_finish_kernel       ctx_all + gelu(mean) * gate_L -> the A operand of h, compute dtype
-//   focal_ln_kernel           LayerNorm over C of fp32 rows (+ fp32 residual): fp32 or compute-dtype rows, and a 16-bit copy
-//   focal_ln_nchw_kernel      LayerNorm over C of the stage's stream -> fp32 NCHW, 64 pixels x 64 channels through LDS
+//   ln_rows_kernel            LayerNorm over C of fp32 rows (+ fp32 residual): fp32 or compute-dtype rows, and a 16-bit copy
+//                             (backbone_rows_core.h's)
+//   focal_ln_nchw_kernel      LayerNorm over C of the stage's stream -> fp32 NCHW, 64 pixels x 64 channels through LDS (the
+//                             shared row statistics, its own transpose)
 //   focal_cast_kernel         fp32 rows -> 16-bit rows (the pre-LN stream in front of a down-sampler, 16-bit mode)
+// The row LayerNorm, the host checks of a rows op and the plan entry points are backbone_rows_core.h's.
 // No atomics; every reduction across workgroups goes through the workspace in a fixed order.
-#include "backbone_conv_core.h"
+#include "backbone_rows_core.h"
 
 namespace sdetr {
 namespace {
@@ -25,7 +28,6 @@ constexpr int kFnThreads = 256;
 constexpr int kFnTW = 8, kFnTH = 16;          // pixel tile of the focal level
 constexpr int kFnCC = 32;                     // its channel chunk
 constexpr int kFnSW = 4;                      // strip width: 16 rows x 2 strips x 8 quads = 256 items
-constexpr int kFnMaxC = 3072;                 // a LayerNorm row in registers: 12 quads per lane
 
 struct FnLevel {
     const float *x;       // ctx_{l-1}: pixel m, channel c at x[m * x_ld + c]
@@ -37,13 +39,6 @@ struct FnLevel {
     int64_t x_ld, gate_ld;
     int batch, h, w, c, tiles_x, tiles_y, accumulate;
 };
-
-__device__ __forceinline__ float fn_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <int K>
 __global__ void __launch_bounds__(kFnThreads) focal_level_kernel(FnLevel a)
@@ -155,63 +150,6 @@ __global__ void __launch_bounds__(kFnThreads) focal_finish_kernel(const float *a
     }
 }
 
-// a row's statistics with the row in registers (one wave per row): mean, then the variance about it
-struct FnRow {
-    float4 v[kFnMaxC / 256];
-    float mean, rstd;
-};
-__device__ __forceinline__ void fn_row_stats(const float *row, int nq, int lane, float inv_c, float eps, FnRow &r)
-{
-    constexpr int kQ = kFnMaxC / 256;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < kQ; ++i) {
-        const int q = lane + 64 * i;
-        r.v[i] = q < nq ? *reinterpret_cast<const float4 *>(row + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (r.v[i].x + r.v[i].y) + (r.v[i].z + r.v[i].w);
-    }
-    r.mean = fn_wave_sum(s) * inv_c;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < kQ; ++i) {
-        if (lane + 64 * i >= nq) continue;
-        const float dx = r.v[i].x - r.mean, dy = r.v[i].y - r.mean, dz = r.v[i].z - r.mean, dw = r.v[i].w - r.mean;
-        ss += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-    r.rstd = 1.f / sqrtf(fn_wave_sum(ss) * inv_c + eps);
-}
-
-// out = (residual +) LayerNorm(x) over C of fp32 rows [rows][C]; out fp32 or compute dtype, out16 (or null) a 16-bit copy
-template <bool F32OUT>
-__global__ void __launch_bounds__(kFnThreads) focal_ln_kernel(const float *x, const float *gamma, const float *beta,
-                                                              const float *res, int64_t rows, int c, float eps, char *out,
-                                                              uint16_t *out16)
-{
-    constexpr int kQ = kFnMaxC / 256;
-    const int lane = threadIdx.x & 63, nq = c >> 2;
-    const int64_t stride = (int64_t)gridDim.x * (kFnThreads / 64);
-    for (int64_t r = (int64_t)blockIdx.x * (kFnThreads / 64) + (threadIdx.x >> 6); r < rows; r += stride) {
-        FnRow row;
-        fn_row_stats(x + r * c, nq, lane, 1.f / (float)c, eps, row);
-#pragma unroll
-        for (int i = 0; i < kQ; ++i) {
-            const int q = lane + 64 * i;
-            if (q >= nq) continue;
-            const float4 g = *reinterpret_cast<const float4 *>(gamma + 4 * q);
-            const float4 be = *reinterpret_cast<const float4 *>(beta + 4 * q);
-            float o0 = fmaf((row.v[i].x - row.mean) * row.rstd, g.x, be.x), o1 = fmaf((row.v[i].y - row.mean) * row.rstd, g.y, be.y);
-            float o2 = fmaf((row.v[i].z - row.mean) * row.rstd, g.z, be.z), o3 = fmaf((row.v[i].w - row.mean) * row.rstd, g.w, be.w);
-            if (res) {
-                const float4 b = *reinterpret_cast<const float4 *>(res + r * c + 4 * q);
-                o0 += b.x, o1 += b.y, o2 += b.z, o3 += b.w;
-            }
-            if (F32OUT) *reinterpret_cast<float4 *>(out + (r * c + 4 * q) * 4) = make_float4(o0, o1, o2, o3);
-            else *reinterpret_cast<uint2 *>(out + (r * c + 4 * q) * 2) = make_uint2(pack_act2(o0, o1), pack_act2(o2, o3));
-            if (out16) *reinterpret_cast<uint2 *>(out16 + r * c + 4 * q) = make_uint2(pack_act2(o0, o1), pack_act2(o2, o3));
-        }
-    }
-}
-
 // LayerNorm over C of x [B][HW][C] -> fp32 NCHW [B][C][HW]: a workgroup owns 64 pixels of one image; one wave per row for
 // the statistics, then 64 channels at a time normalised into an LDS tile and written along the pixels
 __global__ void __launch_bounds__(kFnThreads) focal_ln_nchw_kernel(const float *x, const float *gamma, const float *beta,
@@ -223,8 +161,9 @@ __global__ void __launch_bounds__(kFnThreads) focal_ln_nchw_kernel(const float *
     const int np = min(64, hw - p0), nq = c >> 2;
     const float *img = x + ((int64_t)n * hw + p0) * c;
     for (int p = wave; p < np; p += kFnThreads / 64) {
-        FnRow row;
-        fn_row_stats(img + (int64_t)p * c, nq, lane, 1.f / (float)c, eps, row);
+        LnRow row;
+        ln_row_load(img + (int64_t)p * c, nq, lane, row);
+        ln_row_stats(nq, lane, 1.f / (float)c, eps, row);
         if (lane == 0) stat[p][0] = row.mean, stat[p][1] = row.rstd;
     }
     __syncthreads();
@@ -260,27 +199,16 @@ __global__ void __launch_bounds__(kFnThreads) focal_cast_kernel(const float *x, 
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int tiles_of(int h, int w) { return ((h + kFnTH - 1) / kFnTH) * ((w + kFnTW - 1) / kFnTW); }
 int64_t sums_bytes(const sdetr_focalnet_op &o) { return (int64_t)o.batch * tiles_of(o.height, o.width) * o.in_channels * 4; }
 int64_t finish_bytes(const sdetr_focalnet_op &o) { return sums_bytes(o) + (int64_t)o.batch * o.in_channels * 4; }
 
-int check_shape(const char *what, const sdetr_focalnet_op &o, int precision)
-{
-    if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
-    if (o.batch < 1 || o.height < 1 || o.width < 1 || o.in_channels < 1)
-        return fail("%s: bad shape (batch %d, %d x %d, channels %d)", what, o.batch, o.height, o.width, o.in_channels);
-    if ((int64_t)o.batch * o.height * o.width * o.in_channels >= (int64_t(1) << 29))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    return 0;
-}
-
 // kinds 3 .. 7 work on rows of C = in_channels, a multiple of 32
 int check_rows(const char *what, const sdetr_focalnet_op &o, int precision)
 {
-    if (int rc = check_shape(what, o, precision)) return rc;
-    if (o.in_channels % 32 || o.in_channels > kFnMaxC)
-        return fail("%s: channels must be a multiple of 32 up to %d (got %d)", what, kFnMaxC, o.in_channels);
+    if (int rc = check_rows_shape(what, o.batch, o.height, o.width, o.in_channels, precision)) return rc;
+    if (o.in_channels % 32 || o.in_channels > kRowMaxC)
+        return fail("%s: channels must be a multiple of 32 up to %d (got %d)", what, kRowMaxC, o.in_channels);
     return 0;
 }
 
@@ -288,7 +216,7 @@ int check_rows(const char *what, const sdetr_focalnet_op &o, int precision)
 int make_gemm(const sdetr_focalnet_op &o, int precision, BConv &c)
 {
     const char *what = "sdetr_focalnet (GEMM)";
-    if (int rc = check_shape(what, o, precision)) return rc;
+    if (int rc = check_rows_shape(what, o.batch, o.height, o.width, o.in_channels, precision)) return rc;
     if (!o.x || !o.weight || !o.bias || !o.out) return fail("%s: null tensor", what);
     if (o.out_channels < 1) return fail("%s: bad out_channels %d", what, o.out_channels);
     if (o.kernel_size < 1 || o.kernel_size > 7 || o.stride < 1 || o.stride > 4 || o.padding < 0 || o.padding >= o.kernel_size)
@@ -305,53 +233,14 @@ int make_gemm(const sdetr_focalnet_op &o, int precision, BConv &c)
     if (o.kind != 0 && (o.residual || o.x_nchw)) return fail("%s: only the linear epilogue takes a residual / the NCHW canvas", what);
     if (o.kind == 2 && (!o.q || o.q_ld < o.out_channels || o.q_ld % 4))
         return fail("%s: the product epilogue needs q with q_ld >= out_channels, q_ld %% 4 == 0", what);
-    if (!aligned16(o.x) || !aligned16(o.weight) || !aligned16(o.out) || !aligned16(o.bias) || !aligned16(o.residual) ||
-        (o.kind == 2 && !aligned16(o.q)))
+    if (!all_aligned16(o.x, o.weight, o.out, o.bias, o.residual) || (o.kind == 2 && !aligned16(o.q)))
         return fail("%s: tensors must be 16-byte aligned", what);
-    c.x = reinterpret_cast<const char *>(o.x);
-    c.w = reinterpret_cast<const uint16_t *>(o.weight);
-    c.bias = o.bias;
-    c.res = reinterpret_cast<const char *>(o.residual);
-    c.out = reinterpret_cast<char *>(o.out);
-    c.out_nchw = nullptr;
-    c.partial = nullptr;
+    const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
+                        o.kernel_size, o.stride, o.padding, o.out_height, o.out_width, o.x_nchw, o.splits};
+    if (int rc = fill_conv(what, g, precision, c)) return rc;
     c.q = o.q;
     c.ldq = o.q_ld;
-    c.batch = o.batch;
-    c.ci = o.in_channels;
-    c.h = o.height;
-    c.w_in = o.width;
-    c.co = o.out_channels;
-    c.ks = o.kernel_size;
-    c.stride = o.stride;
-    c.pad = o.padding;
-    c.ho = o.out_height;
-    c.wo = o.out_width;
-    c.relu = 0;
-    c.K = o.in_channels * o.kernel_size * o.kernel_size;
-    c.kpad = round32(c.K);
-    const int64_t M = (int64_t)o.batch * c.ho * c.wo;
-    const int64_t esz = (o.x_nchw || precision == 0) ? 4 : 2;
-    const int64_t x_bytes = (int64_t)o.batch * o.in_channels * o.height * o.width * esz;
-    const int64_t w_bytes = (int64_t)(precision == 0 ? 3 : 1) * o.out_channels * c.kpad * 2;
-    if (M >= (1 << 30) || x_bytes >= (int64_t(1) << 31) || w_bytes >= (int64_t(1) << 31) ||
-        M * o.out_channels >= (int64_t(1) << 31))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    c.M = (int)M;
-    c.x_bytes = (uint32_t)x_bytes;
-    c.w_bytes = (uint32_t)w_bytes;
-    c.plane = (int64_t)o.out_channels * c.kpad;
-    c.splits = resolve_splits(c.M, c.co, c.kpad, o.splits);
-    c.k_per_split = (c.kpad / kBK + c.splits - 1) / c.splits * kBK;
-    c.splits = (c.kpad + c.k_per_split - 1) / c.k_per_split;
     return 0;
-}
-
-template <int EPI>
-void launch_rows_gemm(hipStream_t s, const BConv &c, bool x3)
-{
-    if (x3) launch_conv<true, false, EPI>(s, c);
-    else launch_conv<false, false, EPI>(s, c);
 }
 
 int run_gemm(hipStream_t s, const sdetr_focalnet_op &o, int precision, void *ws, int64_t ws_bytes)
@@ -366,9 +255,7 @@ int run_gemm(hipStream_t s, const sdetr_focalnet_op &o, int precision, void *ws,
     if (o.kind == 1) launch_rows_gemm<1>(s, c, x3);
     else if (o.kind == 2 && o.out_f32) launch_rows_gemm<4>(s, c, x3);
     else if (o.kind == 2) launch_rows_gemm<3>(s, c, x3);
-    else if (o.x_nchw && x3) launch_conv<true, true, 2>(s, c);
-    else if (o.x_nchw) launch_conv<false, true, 2>(s, c);
-    else launch_rows_gemm<2>(s, c, x3);
+    else launch_gemm<2>(s, c, x3, o.x_nchw != 0);
     return check_launch("sdetr_focalnet (GEMM)");
 }
 
@@ -380,8 +267,7 @@ int make_level(const sdetr_focalnet_op &o, int precision, FnLevel &a)
     if (o.kernel_size != 3 && o.kernel_size != 5 && o.kernel_size != 7 && o.kernel_size != 9)
         return fail("%s: kernel size must be 3, 5, 7 or 9 (got %d)", what, o.kernel_size);
     if (o.x_ld < o.in_channels || o.x_ld % 4 || o.q_ld < 1) return fail("%s: bad row strides (x_ld %d, q_ld %d)", what, o.x_ld, o.q_ld);
-    if (!aligned16(o.x) || !aligned16(o.weight) || !aligned16(o.out) || !aligned16(o.out2) ||
-        (reinterpret_cast<uintptr_t>(o.q) & 3))
+    if (!all_aligned16(o.x, o.weight, o.out, o.out2) || (reinterpret_cast<uintptr_t>(o.q) & 3))
         return fail("%s: tensors must be 16-byte aligned", what);
     if ((int64_t)o.batch * o.height * o.width * o.x_ld >= (int64_t(1) << 31)) return fail("%s: tensors too large", what);
     a.x = reinterpret_cast<const float *>(o.x);
@@ -435,7 +321,7 @@ int check_finish(const sdetr_focalnet_op &o, int precision)
     if (int rc = check_rows(what, o, precision)) return rc;
     if (!o.x || !o.q || !o.out) return fail("%s: null tensor", what);
     if (o.q_ld < 1) return fail("%s: bad q_ld %d", what, o.q_ld);
-    if (!aligned16(o.x) || !aligned16(o.out) || (reinterpret_cast<uintptr_t>(o.q) & 3))
+    if (!all_aligned16(o.x, o.out) || (reinterpret_cast<uintptr_t>(o.q) & 3))
         return fail("%s: tensors must be 16-byte aligned", what);
     if (o.batch > 65535) return fail("%s: batch above 65535", what);
     return 0;
@@ -467,13 +353,10 @@ int run_finish(hipStream_t s, const sdetr_focalnet_op &o, int precision, void *w
 int check_ln(const sdetr_focalnet_op &o, int precision)
 {
     const char *what = "sdetr_focalnet (LayerNorm)";
-    if (int rc = check_rows(what, o, precision)) return rc;
-    if (!o.x || !o.gamma || !o.beta || !o.out) return fail("%s: null tensor", what);
+    if (int rc = check_ln_rows(what, o.batch, o.height, o.width, o.in_channels, precision, o.x, o.gamma, o.beta, o.out)) return rc;
     if (o.kind == 6 && (o.residual || o.out2)) return fail("%s: the NCHW form takes no residual / 16-bit copy", what);
     if (o.out2 && precision == 0) return fail("%s: the 16-bit copy exists in 16-bit mode only", what);
-    if (!aligned16(o.x) || !aligned16(o.gamma) || !aligned16(o.beta) || !aligned16(o.out) || !aligned16(o.residual) ||
-        !aligned16(o.out2))
-        return fail("%s: tensors must be 16-byte aligned", what);
+    if (!all_aligned16(o.residual, o.out2)) return fail("%s: tensors must be 16-byte aligned", what);
     if (o.batch > 65535) return fail("%s: batch above 65535", what);
     return 0;
 }
@@ -481,21 +364,14 @@ int check_ln(const sdetr_focalnet_op &o, int precision)
 int run_ln(hipStream_t s, const sdetr_focalnet_op &o, int precision)
 {
     if (int rc = check_ln(o, precision)) return rc;
-    const float *x = reinterpret_cast<const float *>(o.x);
     const int hw = o.height * o.width;
-    if (o.kind == 6) {
-        hipLaunchKernelGGL(focal_ln_nchw_kernel, dim3((unsigned)((hw + 63) / 64), (unsigned)o.batch), dim3(kFnThreads), 0, s, x,
-                           o.gamma, o.beta, hw, o.in_channels, o.eps, reinterpret_cast<float *>(o.out));
-        return check_launch("sdetr_focalnet (LayerNorm)");
-    }
-    const int64_t rows = (int64_t)o.batch * hw;
-    const unsigned blocks = (unsigned)std::min<int64_t>((rows + 3) / 4, 16384);
-    if (precision == 0 || o.out_f32)
-        hipLaunchKernelGGL(focal_ln_kernel<true>, dim3(blocks), dim3(kFnThreads), 0, s, x, o.gamma, o.beta, o.residual, rows,
-                           o.in_channels, o.eps, reinterpret_cast<char *>(o.out), reinterpret_cast<uint16_t *>(o.out2));
+    if (o.kind == 6)
+        hipLaunchKernelGGL(focal_ln_nchw_kernel, dim3((unsigned)((hw + 63) / 64), (unsigned)o.batch), dim3(kFnThreads), 0, s,
+                           reinterpret_cast<const float *>(o.x), o.gamma, o.beta, hw, o.in_channels, o.eps,
+                           reinterpret_cast<float *>(o.out));
     else
-        hipLaunchKernelGGL(focal_ln_kernel<false>, dim3(blocks), dim3(kFnThreads), 0, s, x, o.gamma, o.beta, o.residual, rows,
-                           o.in_channels, o.eps, reinterpret_cast<char *>(o.out), reinterpret_cast<uint16_t *>(o.out2));
+        launch_ln_rows(s, precision == 0 || o.out_f32, o.x, o.gamma, o.beta, o.residual, (int64_t)o.batch * hw, o.in_channels,
+                       o.eps, o.out, o.out2);
     return check_launch("sdetr_focalnet (LayerNorm)");
 }
 
@@ -505,7 +381,7 @@ int check_cast(const sdetr_focalnet_op &o, int precision)
     if (int rc = check_rows(what, o, precision)) return rc;
     if (precision != 1) return fail("%s: 16-bit mode only", what);
     if (!o.x || !o.out) return fail("%s: null tensor", what);
-    if (!aligned16(o.x) || !aligned16(o.out)) return fail("%s: tensors must be 16-byte aligned", what);
+    if (!all_aligned16(o.x, o.out)) return fail("%s: tensors must be 16-byte aligned", what);
     return 0;
 }
 
@@ -560,36 +436,21 @@ int run_op(hipStream_t s, const sdetr_focalnet_op &o, int precision, void *ws, i
 
 using namespace sdetr;
 
+using FocalnetPlan = Plan<sdetr_focalnet_op, check_op, run_op>;
+
 extern "C" int64_t sdetr_focalnet_workspace_bytes(const sdetr_focalnet_op *ops, int n_ops, int precision)
 {
-    if (!ops || n_ops < 1) return -1;
-    int64_t most = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        int64_t need;
-        if (check_op(ops[i], precision, need)) return -1;
-        most = std::max(most, need);
-    }
-    return most;
+    return FocalnetPlan::workspace_bytes(ops, n_ops, precision);
 }
 
 extern "C" int sdetr_focalnet_op_run(sdetr_stream_t stream, const sdetr_focalnet_op *op, int precision, void *workspace,
                                      int64_t workspace_bytes)
 {
-    if (!op) return fail("sdetr_focalnet_op_run: null op");
-    return run_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
+    return FocalnetPlan::op_run("sdetr_focalnet", stream, op, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_focalnet_run(sdetr_stream_t stream, const sdetr_focalnet_op *ops, int n_ops, int precision,
                                   void *workspace, int64_t workspace_bytes)
 {
-    if (!ops || n_ops < 1) return fail("sdetr_focalnet_run: empty plan");
-    for (int i = 0; i < n_ops; ++i) {   // validate the whole plan before the first launch
-        int64_t need;
-        if (check_op(ops[i], precision, need)) return SDETR_EINVAL;
-        if (need > workspace_bytes || (need && !workspace))
-            return fail("sdetr_focalnet_run: op %d needs %lld workspace bytes (workspace too small)", i, (long long)need);
-    }
-    for (int i = 0; i < n_ops; ++i)
-        if (int rc = run_op((hipStream_t)stream, ops[i], precision, workspace, workspace_bytes)) return rc;
-    return 0;
+    return FocalnetPlan::run("sdetr_focalnet", stream, ops, n_ops, precision, workspace, workspace_bytes);
 }

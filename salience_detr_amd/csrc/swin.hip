@@ -5,90 +5,25 @@
 //   the GEMMs                 backbone_conv_core.h's implicit-GEMM kernel: proj / fc2 / the merging reduction / the 4x4
 //                             stem on the NCHW canvas (EPI 2, fp32 stream, + residual, + NCHW copy), fc1 + GELU (EPI 1),
 //                             qkv (EPI 5: acc + b in the compute dtype)
-//   swin_ln_kernel            LayerNorm over C of fp32 rows, one wave per row, the row in registers
+//   ln_rows_kernel            LayerNorm over C of fp32 rows, one wave per row, the row in registers (backbone_rows_core.h's)
 //   swin_attention_kernel     one workgroup per (window, head): the window's q / k / v of that head staged in LDS (tokens of
 //                             the zero padding synthesised from the qkv bias, the roll as index arithmetic), S^T = K Q^T
 //                             per 16-query tile with all of a query's scores in registers, two-pass softmax in fp32, the
 //                             scores as the B operand of O^T = V^T P^T.  16-bit: v_mfma_f32_16x16x32 (the head dimension is
 //                             ONE k-step); fp32: v_mfma_f32_16x16x4_f32 on fp32 operands -- S never touches LDS
-//   swin_merge_ln_kernel      the 2 x 2 gather of a patch merging + LayerNorm over 4 C, one wave per output row
+//   swin_merge_ln_kernel      the 2 x 2 gather of a patch merging + LayerNorm over 4 C, one wave per output row (its own
+//                             gather, the shared row statistics and write)
+// The row LayerNorm, the host checks of a rows op and the plan entry points are backbone_rows_core.h's.
 // No atomics; every launch writes every element of its outputs.
-#include "backbone_conv_core.h"
+#include "backbone_rows_core.h"
 
 namespace sdetr {
 namespace {
 
 constexpr int kSwThreads = 256;
-constexpr int kSwMaxC = 3072;                 // a LayerNorm row in registers: 12 quads per lane
 constexpr int kSwHd = 32;                     // the head dimension of every V1 arch
 
 typedef float sw_f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sw_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// mean, then the variance about it, of a row held as kQ quads per lane (quads past nq are zeros and do not count)
-struct SwRow {
-    float4 v[kSwMaxC / 256];
-    float mean, rstd;
-};
-__device__ __forceinline__ void sw_row_stats(int nq, int lane, float inv_c, float eps, SwRow &r)
-{
-    constexpr int kQ = kSwMaxC / 256;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < kQ; ++i) s += (r.v[i].x + r.v[i].y) + (r.v[i].z + r.v[i].w);
-    r.mean = sw_wave_sum(s) * inv_c;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < kQ; ++i) {
-        if (lane + 64 * i >= nq) continue;
-        const float dx = r.v[i].x - r.mean, dy = r.v[i].y - r.mean, dz = r.v[i].z - r.mean, dw = r.v[i].w - r.mean;
-        ss += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-    r.rstd = 1.f / sqrtf(sw_wave_sum(ss) * inv_c + eps);
-}
-
-template <bool F32OUT>
-__device__ __forceinline__ void sw_row_write(const SwRow &row, const float *gamma, const float *beta, int nq, int lane, char *out)
-{
-    constexpr int kQ = kSwMaxC / 256;
-#pragma unroll
-    for (int i = 0; i < kQ; ++i) {
-        const int q = lane + 64 * i;
-        if (q >= nq) continue;
-        const float4 g = *reinterpret_cast<const float4 *>(gamma + 4 * q);
-        const float4 be = *reinterpret_cast<const float4 *>(beta + 4 * q);
-        const float o0 = fmaf((row.v[i].x - row.mean) * row.rstd, g.x, be.x), o1 = fmaf((row.v[i].y - row.mean) * row.rstd, g.y, be.y);
-        const float o2 = fmaf((row.v[i].z - row.mean) * row.rstd, g.z, be.z), o3 = fmaf((row.v[i].w - row.mean) * row.rstd, g.w, be.w);
-        if (F32OUT) *reinterpret_cast<float4 *>(out + (int64_t)q * 16) = make_float4(o0, o1, o2, o3);
-        else *reinterpret_cast<uint2 *>(out + (int64_t)q * 8) = make_uint2(pack_act2(o0, o1), pack_act2(o2, o3));
-    }
-}
-
-// out = LayerNorm(x) over C of fp32 rows [rows][C]; out fp32 or compute dtype
-template <bool F32OUT>
-__global__ void __launch_bounds__(kSwThreads) swin_ln_kernel(const float *x, const float *gamma, const float *beta, int64_t rows,
-                                                             int c, float eps, char *out)
-{
-    constexpr int kQ = kSwMaxC / 256;
-    const int lane = threadIdx.x & 63, nq = c >> 2;
-    const int64_t stride = (int64_t)gridDim.x * (kSwThreads / 64);
-    for (int64_t r = (int64_t)blockIdx.x * (kSwThreads / 64) + (threadIdx.x >> 6); r < rows; r += stride) {
-        SwRow row;
-#pragma unroll
-        for (int i = 0; i < kQ; ++i) {
-            const int q = lane + 64 * i;
-            row.v[i] = q < nq ? *reinterpret_cast<const float4 *>(x + r * c + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        sw_row_stats(nq, lane, 1.f / (float)c, eps, row);
-        sw_row_write<F32OUT>(row, gamma, beta, nq, lane, out + r * c * (F32OUT ? 4 : 2));
-    }
-}
 
 // x fp32 [B][H][W][C] -> out [B][Ho][Wo][4 C], row (i, j) = LN([x(2i, 2j) | x(2i + 1, 2j) | x(2i, 2j + 1) | x(2i + 1, 2j + 1)]):
 // the row parity varies first; pixels past an odd H / W are zeros inside the statistics
@@ -96,15 +31,14 @@ template <bool F32OUT>
 __global__ void __launch_bounds__(kSwThreads) swin_merge_ln_kernel(const float *x, const float *gamma, const float *beta, int batch,
                                                                    int h, int w, int c, float eps, char *out)
 {
-    constexpr int kQ = kSwMaxC / 256;
     const int lane = threadIdx.x & 63, cq = c >> 2, nq = c;          // 4 C / 4 quads per output row
     const int ho = (h + 1) >> 1, wo = (w + 1) >> 1;
     const int64_t rows = (int64_t)batch * ho * wo, stride = (int64_t)gridDim.x * (kSwThreads / 64);
     for (int64_t r = (int64_t)blockIdx.x * (kSwThreads / 64) + (threadIdx.x >> 6); r < rows; r += stride) {
         const int n = (int)(r / (ho * wo)), rem = (int)(r - (int64_t)n * ho * wo), oy = rem / wo, ox = rem - oy * wo;
-        SwRow row;
+        LnRow row;
 #pragma unroll
-        for (int i = 0; i < kQ; ++i) {
+        for (int i = 0; i < kRowQuads; ++i) {
             const int q = lane + 64 * i;
             row.v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (q >= nq) continue;
@@ -112,8 +46,8 @@ __global__ void __launch_bounds__(kSwThreads) swin_merge_ln_kernel(const float *
             if (iy < h && ix < w)
                 row.v[i] = *reinterpret_cast<const float4 *>(x + (((int64_t)n * h + iy) * w + ix) * c + 4 * (q - part * cq));
         }
-        sw_row_stats(nq, lane, 1.f / (float)(4 * c), eps, row);
-        sw_row_write<F32OUT>(row, gamma, beta, nq, lane, out + r * 4 * c * (F32OUT ? 4 : 2));
+        ln_row_stats(nq, lane, 1.f / (float)(4 * c), eps, row);
+        ln_row_write<F32OUT>(row, gamma, beta, nullptr, nq, lane, out + r * 4 * c * (F32OUT ? 4 : 2), nullptr);
     }
 }
 
@@ -306,16 +240,9 @@ __global__ void __launch_bounds__(kSwThreads) swin_attention_kernel(SwAttn a)
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_shape(const char *what, const sdetr_swin_op &o, int precision)
 {
-    if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
-    if (o.batch < 1 || o.height < 1 || o.width < 1 || o.in_channels < 1)
-        return fail("%s: bad shape (batch %d, %d x %d, channels %d)", what, o.batch, o.height, o.width, o.in_channels);
-    if ((int64_t)o.batch * o.height * o.width * o.in_channels >= (int64_t(1) << 29))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    return 0;
+    return check_rows_shape(what, o.batch, o.height, o.width, o.in_channels, precision);
 }
 
 // a GEMM op (kinds 0 .. 2) as the conv kernel's arguments
@@ -331,54 +258,15 @@ int make_gemm(const sdetr_swin_op &o, int precision, BConv &c)
         return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
     if (o.kind != 0 && (o.residual || o.out_nchw || o.x_nchw || o.kernel_size != 1))
         return fail("%s: only the linear epilogue takes a residual / the NCHW canvas / a patch / writes the NCHW copy", what);
-    if (!aligned16(o.x) || !aligned16(o.weight) || !aligned16(o.bias) || !aligned16(o.out) || !aligned16(o.residual) ||
-        !aligned16(o.out_nchw))
+    if (!all_aligned16(o.x, o.weight, o.bias, o.out, o.residual, o.out_nchw))
         return fail("%s: tensors must be 16-byte aligned", what);
-    c.x = reinterpret_cast<const char *>(o.x);
-    c.w = reinterpret_cast<const uint16_t *>(o.weight);
-    c.bias = o.bias;
-    c.res = reinterpret_cast<const char *>(o.residual);
-    c.out = reinterpret_cast<char *>(o.out);
-    c.out_nchw = o.out_nchw;
-    c.partial = nullptr;
-    c.q = nullptr;
-    c.ldq = 0;
-    c.batch = o.batch;
-    c.ci = o.in_channels;
-    c.h = o.height;
-    c.w_in = o.width;
-    c.co = o.out_channels;
-    c.ks = o.kernel_size;
-    c.stride = o.stride;
-    c.pad = 0;
-    c.ho = out_hw(o.height, o.kernel_size, o.stride, 0);
-    c.wo = out_hw(o.width, o.kernel_size, o.stride, 0);
     if (o.height < o.kernel_size || o.width < o.kernel_size) return fail("%s: empty output", what);
-    c.relu = 0;
-    c.K = o.in_channels * o.kernel_size * o.kernel_size;
-    c.kpad = round32(c.K);
-    const int64_t M = (int64_t)o.batch * c.ho * c.wo;
-    const int64_t esz = (o.x_nchw || precision == 0) ? 4 : 2;
-    const int64_t x_bytes = (int64_t)o.batch * o.in_channels * o.height * o.width * esz;
-    const int64_t w_bytes = (int64_t)(precision == 0 ? 3 : 1) * o.out_channels * c.kpad * 2;
-    if (M >= (1 << 30) || x_bytes >= (int64_t(1) << 31) || w_bytes >= (int64_t(1) << 31) ||
-        M * o.out_channels >= (int64_t(1) << 31))
-        return fail("%s: tensors too large for 32-bit offsets", what);
-    c.M = (int)M;
-    c.x_bytes = (uint32_t)x_bytes;
-    c.w_bytes = (uint32_t)w_bytes;
-    c.plane = (int64_t)o.out_channels * c.kpad;
-    c.splits = resolve_splits(c.M, c.co, c.kpad, o.splits);
-    c.k_per_split = (c.kpad / kBK + c.splits - 1) / c.splits * kBK;
-    c.splits = (c.kpad + c.k_per_split - 1) / c.k_per_split;
+    const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
+                        o.kernel_size, o.stride, 0, out_hw(o.height, o.kernel_size, o.stride, 0),
+                        out_hw(o.width, o.kernel_size, o.stride, 0), o.x_nchw, o.splits};
+    if (int rc = fill_conv(what, g, precision, c)) return rc;
+    c.out_nchw = o.out_nchw;
     return 0;
-}
-
-template <int EPI>
-void launch_rows_gemm(hipStream_t s, const BConv &c, bool x3)
-{
-    if (x3) launch_conv<true, false, EPI>(s, c);
-    else launch_conv<false, false, EPI>(s, c);
 }
 
 int run_gemm(hipStream_t s, const sdetr_swin_op &o, int precision, void *ws, int64_t ws_bytes)
@@ -392,36 +280,20 @@ int run_gemm(hipStream_t s, const sdetr_swin_op &o, int precision, void *ws, int
     const bool x3 = precision == 0;
     if (o.kind == 1) launch_rows_gemm<1>(s, c, x3);
     else if (o.kind == 2) launch_rows_gemm<5>(s, c, x3);
-    else if (o.x_nchw && x3) launch_conv<true, true, 2>(s, c);
-    else if (o.x_nchw) launch_conv<false, true, 2>(s, c);
-    else launch_rows_gemm<2>(s, c, x3);
+    else launch_gemm<2>(s, c, x3, o.x_nchw != 0);
     return check_launch("sdetr_swin (GEMM)");
 }
 
 int check_ln(const sdetr_swin_op &o, int precision)
 {
-    const char *what = "sdetr_swin (LayerNorm)";
-    if (int rc = check_shape(what, o, precision)) return rc;
-    if (o.in_channels % 32 || o.in_channels > kSwMaxC)
-        return fail("%s: channels must be a multiple of 32 up to %d (got %d)", what, kSwMaxC, o.in_channels);
-    if (!o.x || !o.gamma || !o.beta || !o.out) return fail("%s: null tensor", what);
-    if (!aligned16(o.x) || !aligned16(o.gamma) || !aligned16(o.beta) || !aligned16(o.out))
-        return fail("%s: tensors must be 16-byte aligned", what);
-    return 0;
+    return check_ln_rows("sdetr_swin (LayerNorm)", o.batch, o.height, o.width, o.in_channels, precision, o.x, o.gamma, o.beta, o.out);
 }
 
 int run_ln(hipStream_t s, const sdetr_swin_op &o, int precision)
 {
     if (int rc = check_ln(o, precision)) return rc;
-    const int64_t rows = (int64_t)o.batch * o.height * o.width;
-    const unsigned blocks = (unsigned)std::min<int64_t>((rows + 3) / 4, 16384);
-    const float *x = reinterpret_cast<const float *>(o.x);
-    if (precision == 0 || o.out_f32)
-        hipLaunchKernelGGL(swin_ln_kernel<true>, dim3(blocks), dim3(kSwThreads), 0, s, x, o.gamma, o.beta, rows, o.in_channels,
-                           o.eps, reinterpret_cast<char *>(o.out));
-    else
-        hipLaunchKernelGGL(swin_ln_kernel<false>, dim3(blocks), dim3(kSwThreads), 0, s, x, o.gamma, o.beta, rows, o.in_channels,
-                           o.eps, reinterpret_cast<char *>(o.out));
+    launch_ln_rows(s, precision == 0 || o.out_f32, o.x, o.gamma, o.beta, nullptr, (int64_t)o.batch * o.height * o.width,
+                   o.in_channels, o.eps, o.out, nullptr);
     return check_launch("sdetr_swin (LayerNorm)");
 }
 
@@ -429,10 +301,10 @@ int check_merge(const sdetr_swin_op &o, int precision)
 {
     const char *what = "sdetr_swin (patch merging)";
     if (int rc = check_shape(what, o, precision)) return rc;
-    if ((4 * o.in_channels) % 32 || 4 * o.in_channels > kSwMaxC)
-        return fail("%s: 4 C must be a multiple of 32 up to %d (got C = %d)", what, kSwMaxC, o.in_channels);
+    if ((4 * o.in_channels) % 32 || 4 * o.in_channels > kRowMaxC)
+        return fail("%s: 4 C must be a multiple of 32 up to %d (got C = %d)", what, kRowMaxC, o.in_channels);
     if (!o.x || !o.gamma || !o.beta || !o.out) return fail("%s: null tensor", what);
-    if (!aligned16(o.x) || !aligned16(o.gamma) || !aligned16(o.beta) || !aligned16(o.out))
+    if (!all_aligned16(o.x, o.gamma, o.beta, o.out))
         return fail("%s: tensors must be 16-byte aligned", what);
     return 0;
 }
@@ -463,7 +335,7 @@ int make_attention(const sdetr_swin_op &o, int precision, SwAttn &a)
     if (o.shift < 0 || o.shift >= o.window) return fail("%s: shift must lie in [0, window) (got %d)", what, o.shift);
     if (!o.x || !o.bias || !o.table || !o.out) return fail("%s: null tensor", what);
     if (o.x == o.out) return fail("%s: x must not alias out", what);
-    if (!aligned16(o.x) || !aligned16(o.bias) || !aligned16(o.table) || !aligned16(o.out))
+    if (!all_aligned16(o.x, o.bias, o.table, o.out))
         return fail("%s: tensors must be 16-byte aligned", what);
     a.qkv = reinterpret_cast<const char *>(o.x);
     a.bias = o.bias;
@@ -538,38 +410,21 @@ int run_op(hipStream_t s, const sdetr_swin_op &o, int precision, void *ws, int64
 
 using namespace sdetr;
 
+using SwinPlan = Plan<sdetr_swin_op, check_op, run_op>;
+
 extern "C" int64_t sdetr_swin_workspace_bytes(const sdetr_swin_op *ops, int n_ops, int precision)
 {
-    if (!ops || n_ops < 1) return -1;
-    int64_t most = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        int64_t need;
-        if (check_op(ops[i], precision, need)) return -1;
-        most = std::max(most, need);
-    }
-    return most;
+    return SwinPlan::workspace_bytes(ops, n_ops, precision);
 }
 
 extern "C" int sdetr_swin_op_run(sdetr_stream_t stream, const sdetr_swin_op *op, int precision, void *workspace,
                                  int64_t workspace_bytes)
 {
-    if (!op) return fail("sdetr_swin_op_run: null op");
-    int64_t need;
-    if (check_op(*op, precision, need)) return SDETR_EINVAL;
-    return run_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
+    return SwinPlan::op_run("sdetr_swin", stream, op, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_swin_run(sdetr_stream_t stream, const sdetr_swin_op *ops, int n_ops, int precision, void *workspace,
                               int64_t workspace_bytes)
 {
-    if (!ops || n_ops < 1) return fail("sdetr_swin_run: empty plan");
-    for (int i = 0; i < n_ops; ++i) {   // validate the whole plan before the first launch
-        int64_t need;
-        if (check_op(ops[i], precision, need)) return SDETR_EINVAL;
-        if (need > workspace_bytes || (need && !workspace))
-            return fail("sdetr_swin_run: op %d needs %lld workspace bytes (workspace too small)", i, (long long)need);
-    }
-    for (int i = 0; i < n_ops; ++i)
-        if (int rc = run_op((hipStream_t)stream, ops[i], precision, workspace, workspace_bytes)) return rc;
-    return 0;
+    return SwinPlan::run("sdetr_swin", stream, ops, n_ops, precision, workspace, workspace_bytes);
 }

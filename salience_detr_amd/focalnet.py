@@ -26,7 +26,6 @@ work, gates, means, LayerNorm statistics and ``q`` stay fp32.  A call with grad 
 takes the plain-torch composite, which is the autograd path; FocalNet backward in HIP is out of scope.  A CPU tensor on
 the HIP form raises: the hot path has no CPU fallback.
 """
-import os
 from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -35,10 +34,10 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .convnext import StochasticDepth
+from .backbone_base import HipBackbone, PlanBuilder, StochasticDepth
 from .derived import derived
 
-MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/focalnet.hip)
+MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/backbone_rows_core.h)
 FOCAL_KERNELS = (3, 5, 7, 9)
 
 
@@ -222,7 +221,7 @@ def _ceil_div(a: int, b: int) -> int:
     return -(-a // b)
 
 
-class FocalNetBackbone(nn.Module):
+class FocalNetBackbone(HipBackbone):
     def __init__(self, arch: Optional[str], weights: Union[None, str, Dict[str, Tensor]] = None,
                  return_indices: Tuple[int, ...] = (0, 1, 2, 3), freeze_indices: Tuple[int, ...] = (), **kwargs):
         super().__init__()
@@ -260,33 +259,6 @@ class FocalNetBackbone(nn.Module):
     def post(self) -> PostNorms:
         return self._modules["1"]
 
-    @staticmethod
-    def _freeze(module: nn.Module):
-        module.eval()
-        for p in module.parameters():
-            p.requires_grad = False
-
-    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
-        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
-        match are skipped (``util.utils.load_state_dict`` of the reference).  Never downloads."""
-        if isinstance(weights, str):
-            if not os.path.exists(weights):
-                raise FileNotFoundError(f"FocalNetBackbone: no weight file at {weights} (nothing is downloaded)")
-            weights = torch.load(weights, map_location="cpu")
-        if "model" in weights and isinstance(weights["model"], dict):
-            weights = weights["model"]
-        own = self.state_dict()
-        matched = {k: v for k, v in weights.items() if k not in own or own[k].shape == v.shape}
-        return self.load_state_dict(matched, strict=False)
-
-    def set_dtype(self, dtype: torch.dtype):
-        """Precision of the products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16`` (one
-        16-bit product, fp32 accumulation, 16-bit GEMM operands; the residual stream stays fp32).  Outputs are fp32."""
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError(f"FocalNetBackbone.set_dtype: {dtype} is not float32 / bfloat16 / float16")
-        self.compute_dtype = dtype
-        return self
-
     # ------------------------------------------------------------------------------------------ form checks
     def _embeds(self) -> List[PatchEmbed]:
         return [self.body.patch_embed] + [s.downsample for s in self.body.layers if hasattr(s, "downsample")]
@@ -312,17 +284,6 @@ class FocalNetBackbone(nn.Module):
         return all(type(n) is nn.LayerNorm and len(n.normalized_shape) == 1 and n.elementwise_affine and n.bias is not None
                    for n in norms)
 
-    def _needs_autograd(self, x: Tensor) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        return x.requires_grad or any(p.requires_grad for p in self.parameters())
-
-    # ------------------------------------------------------------------------------------------ forward
-    def forward(self, x: Tensor) -> Dict[str, Tensor]:
-        if self._needs_autograd(x) or not self.hip_form():
-            return self.forward_torch(x)
-        return self.forward_hip(x)
-
     def forward_torch(self, x: Tensor) -> Dict[str, Tensor]:
         """The differentiable composite (the holder modules themselves) on the input's device."""
         outs = {}
@@ -335,48 +296,6 @@ class FocalNetBackbone(nn.Module):
                 x = stage.downsample(x)
         return {f"layers.{i}.blocks": outs[f"layers.{i}.blocks"] for i in self.return_indices}
 
-    def _precision(self) -> int:
-        return 0 if self.compute_dtype == torch.float32 else 1
-
-    def _lib(self):
-        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
-
-    def _packed(self, layer: nn.Module, layout: int = 0, scale: Union[None, float, Tensor] = None, scale_bias: bool = True,
-                pad_to: int = 1) -> Tuple[Tensor, Tensor]:
-        """``(packed weight, bias)`` of a conv or Linear for the implicit GEMM (``sdetr_backbone_pack`` with a unit norm):
-        ``scale`` (a layer scale, or the modulator's ``1 / (L + 1)``) folded into the weight and, with ``scale_bias``, the
-        bias; the output width zero-padded to a multiple of ``pad_to``.  Built once per parameter version, precision and
-        compute dtype."""
-        precision, lib = self._precision(), self._lib()
-        w = layer.weight
-        co, ci, k = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
-        cop = _ceil_div(co, pad_to) * pad_to
-
-        def build():
-            dev = w.device
-            w32 = torch.zeros((cop, ci, k, k), dtype=torch.float32, device=dev)
-            w32[:co] = w.detach().to(torch.float32).reshape(co, ci, k, k)
-            b32 = torch.zeros(cop, dtype=torch.float32, device=dev)
-            b32[:co] = layer.bias.detach().to(torch.float32)
-            gamma = torch.ones(cop, device=dev)
-            if isinstance(scale, Tensor):
-                gamma[:co] = scale.detach().to(torch.float32).reshape(co)
-            elif scale is not None:
-                gamma *= float(scale)
-            beta = (b32 * gamma if scale_bias else b32).contiguous()
-            zeros, ones = torch.zeros(cop, device=dev), torch.ones(cop, device=dev)
-            nbytes = lib.sdetr_backbone_packed_bytes(cop, ci, k, precision)
-            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=dev)
-            bias = torch.empty(cop, dtype=torch.float32, device=dev)
-            _hip.launch("sdetr_backbone_pack", lib, dev, w32.data_ptr(), gamma.data_ptr(), beta.data_ptr(), zeros.data_ptr(),
-                        ones.data_ptr(), 0.0, cop, ci, k, layout, precision, packed.data_ptr(), bias.data_ptr(),
-                        what="FocalNetBackbone (pack)")
-            return packed, bias
-        sources = (w, layer.bias) + ((scale,) if isinstance(scale, Tensor) else ())
-        fixed = None if isinstance(scale, Tensor) else scale
-        return derived(layer, "focalnet_packed", sources, build,
-                       extra=(precision, self.compute_dtype, layout, fixed, scale_bias, pad_to))
-
     def _taps(self, conv: nn.Conv2d) -> Tensor:
         """The depthwise taps tap-major ``[k * k, C]``, fp32."""
         def build():
@@ -384,41 +303,16 @@ class FocalNetBackbone(nn.Module):
             return conv.weight.detach().to(torch.float32).reshape(c, k * k).t().contiguous()
         return derived(conv, "focalnet_taps", (conv.weight,), build)
 
-    def _affine(self, norm: nn.LayerNorm, scale: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        """The LayerNorm's affine in fp32, a layer scale folded in: ``g * (w n + b) = (g w) n + g b``."""
-        def build():
-            w, b = norm.weight.detach().to(torch.float32), norm.bias.detach().to(torch.float32)
-            if scale is not None:
-                g = scale.detach().to(torch.float32)
-                w, b = w * g, b * g
-            return w.contiguous(), b.contiguous()
-        return derived(norm, "focalnet_affine", (norm.weight, norm.bias, scale), build)
-
     def build_plan(self, x: Tensor, splits: int = 0):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
         ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op.
         The buffers of a stage are shared by its blocks (the launches of a plan run in order on one stream)."""
         p16 = self._precision() == 1
         act = self.compute_dtype if p16 else torch.float32
-        dev, batch = x.device, x.shape[0]
-        ops: List[_hip.FocalnetOpStruct] = []
-        names: List[str] = []
-        keep: List[Tensor] = [x]
-        outputs: Dict[str, Tensor] = {}
-
-        def new(shape, dtype):
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def op(name, kind, **kw):
-            f = dict(kind=kind, x=None, weight=None, bias=None, gamma=None, beta=None, residual=None, q=None, out=None,
-                     out2=None, batch=batch, in_channels=0, height=1, width=1, out_channels=0, out_height=1, out_width=1,
-                     kernel_size=1, stride=1, padding=0, x_nchw=0, out_f32=0, x_ld=0, q_ld=0, accumulate=0, last=0,
-                     splits=splits, eps=0.0)
-            f.update(kw)
-            ops.append(_hip.FocalnetOpStruct(**f))
-            names.append(name)
+        batch = x.shape[0]
+        pb = PlanBuilder(_hip.FocalnetOpStruct, x, batch=batch, height=1, width=1, out_height=1, out_width=1, kernel_size=1,
+                         stride=1, splits=splits)
+        new, op, keep, outputs = pb.new, pb.op, pb.keep, pb.outputs
 
         def gemm(name, kind, layer, src, out, h, w, ho=None, wo=None, layout=0, **kw):
             pack = {k: kw.pop(k) for k in ("scale", "scale_bias", "pad_to") if k in kw}
@@ -430,11 +324,8 @@ class FocalNetBackbone(nn.Module):
                out_width=wo or w, kernel_size=k, stride=s, padding=p, x_nchw=layout, **kw)
 
         def layer_norm(name, norm, src, out, h, w, c, out_f32, scale=None, residual=None, out2=None, nchw=False):
-            gamma, beta = self._affine(norm, scale)
-            keep.extend((gamma, beta))
-            op(name, 6 if nchw else 5, x=src.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), residual=_hip.ptr(residual),
-               out=out.data_ptr(), out2=_hip.ptr(out2), in_channels=c, height=h, width=w, out_channels=c,
-               out_f32=1 if out_f32 else 0, eps=float(norm.eps))
+            pb.layer_norm(name, 6 if nchw else 5, self._affine(norm, scale), norm.eps, src, out, h, w, c, out_f32,
+                          residual=_hip.ptr(residual), out2=_hip.ptr(out2))
 
         def embed(name, emb, src, h, w, layout, copy):
             """conv + LayerNorm of a patch embedding: the new stream, its 16-bit copy (or None), and its size"""
@@ -522,7 +413,7 @@ class FocalNetBackbone(nn.Module):
                     src = stream16
                 stream, stream16, h, w, c = embed(f"0.layers.{i}.downsample", stage.downsample, src, h, w, 0, copy)
         outputs = {f"layers.{i}.blocks": outputs[f"layers.{i}.blocks"] for i in self.return_indices}
-        return ops, outputs, keep, names
+        return pb.ops, outputs, keep, pb.names
 
     def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
         if x.dtype != torch.float32:
@@ -533,12 +424,5 @@ class FocalNetBackbone(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"FocalNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
         ops, outputs, keep, _ = self.build_plan(x, splits)
-        lib, precision = self._lib(), self._precision()
-        arr = (_hip.FocalnetOpStruct * len(ops))(*ops)
-        ws_bytes = lib.sdetr_focalnet_workspace_bytes(arr, len(ops), precision)
-        if ws_bytes < 0:
-            _hip.check(-1, "FocalNetBackbone (workspace)", lib)
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
-        _hip.launch("sdetr_focalnet_run", lib, x.device, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
-                    what="FocalNetBackbone (run)")
+        self._run_plan(_hip.FocalnetOpStruct, "sdetr_focalnet", ops, x.device)
         return outputs

@@ -27,7 +27,6 @@ takes the plain-torch composite, which is the autograd path; a Swin backward in 
 with a window other than 7 / 12 or a head dimension other than 32 run the composite too (``hip_form()`` is False).  A CPU
 tensor on the HIP form raises: the hot path has no CPU fallback.
 """
-import os
 from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -36,21 +35,12 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .convnext import StochasticDepth
+from .backbone_base import HipBackbone, Permute, PlanBuilder, StochasticDepth
 from .derived import derived
 
-MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/swin.hip); the merging norm sees 4 C
+MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/backbone_rows_core.h); the merging norm sees 4 C
 WINDOWS = (7, 12)
 HEAD_DIM = 32
-
-
-class Permute(nn.Module):
-    def __init__(self, dims: Sequence[int]):
-        super().__init__()
-        self.dims = tuple(dims)
-
-    def forward(self, x: Tensor) -> Tensor:
-        return x.permute(*self.dims)
 
 
 def _axis_regions(padded: int, window: int, shift: int, device) -> Tensor:
@@ -213,7 +203,7 @@ ARCHS = {
 V2_ARCHS = ("swin_v2_t", "swin_v2_b")
 
 
-class SwinBackbone(nn.Module):
+class SwinBackbone(HipBackbone):
     def __init__(self, arch: Optional[str], weights: Union[None, str, Dict[str, Tensor]] = None,
                  return_indices: Tuple[int, ...] = (0, 1, 2, 3), freeze_indices: Tuple[int, ...] = (), **kwargs):
         super().__init__()
@@ -257,36 +247,12 @@ class SwinBackbone(nn.Module):
     def body(self) -> SwinTransformer:
         return self._modules["0"]
 
-    @staticmethod
-    def _freeze(module: nn.Module):
-        module.eval()
-        for p in module.parameters():
-            p.requires_grad = False
-
-    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
-        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
-        match are skipped.  A full ``SwinTransformer`` checkpoint (keys ``features.*``, ``norm.*``, ``head.*``) is taken
-        too: what the extractor does not keep is dropped.  Never downloads."""
-        if isinstance(weights, str):
-            if not os.path.exists(weights):
-                raise FileNotFoundError(f"SwinBackbone: no weight file at {weights} (nothing is downloaded)")
-            weights = torch.load(weights, map_location="cpu")
-        if "model" in weights and isinstance(weights["model"], dict):
-            weights = weights["model"]
-        own = self.state_dict()
+    def _remap_checkpoint_keys(self, weights: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """A full ``SwinTransformer`` checkpoint (keys ``features.*``, ``norm.*``, ``head.*``) is taken too: what the
+        extractor does not keep is dropped."""
         if not any(k.startswith("0.") for k in weights):
             weights = {"0." + k: v for k, v in weights.items()}
-        matched = {k: v for k, v in weights.items() if k not in own or own[k].shape == v.shape}
-        return self.load_state_dict(matched, strict=False)
-
-    def set_dtype(self, dtype: torch.dtype):
-        """Precision of the products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16`` (one
-        16-bit product, fp32 accumulation, 16-bit rows between launches; the residual stream stays fp32).  Outputs are
-        fp32."""
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError(f"SwinBackbone.set_dtype: {dtype} is not float32 / bfloat16 / float16")
-        self.compute_dtype = dtype
-        return self
+        return weights
 
     # ------------------------------------------------------------------------------------------ form checks
     def _stages(self):
@@ -322,17 +288,6 @@ class SwinBackbone(nn.Module):
         return all(type(n) is nn.LayerNorm and len(n.normalized_shape) == 1 and n.elementwise_affine and n.bias is not None
                    for n in norms)
 
-    def _needs_autograd(self, x: Tensor) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        return x.requires_grad or any(p.requires_grad for p in self.parameters())
-
-    # ------------------------------------------------------------------------------------------ forward
-    def forward(self, x: Tensor) -> Dict[str, Tensor]:
-        if self._needs_autograd(x) or not self.hip_form():
-            return self.forward_torch(x)
-        return self.forward_hip(x)
-
     def forward_torch(self, x: Tensor) -> Dict[str, Tensor]:
         """The differentiable composite (the holder modules themselves) on the input's device."""
         outs = {}
@@ -346,38 +301,6 @@ class SwinBackbone(nn.Module):
                 x = merging(x)
         outs = self._modules["1"](outs)
         return {f"features.{2 * i + 1}": outs[f"features.{2 * i + 1}"].contiguous() for i in self.return_indices}
-
-    def _precision(self) -> int:
-        return 0 if self.compute_dtype == torch.float32 else 1
-
-    def _lib(self):
-        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
-
-    def _packed(self, layer: nn.Module, layout: int = 0) -> Tuple[Tensor, Tensor]:
-        """``(packed weight, bias)`` of a conv or Linear for the implicit GEMM (``sdetr_backbone_pack`` with a unit norm);
-        a Linear without a bias gets zeros.  Built once per parameter version, precision and compute dtype."""
-        precision, lib = self._precision(), self._lib()
-        w = layer.weight
-        co, ci, k = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
-
-        def build():
-            dev = w.device
-            w32 = w.detach().to(torch.float32).reshape(co, ci, k, k).contiguous()
-            zeros, ones = torch.zeros(co, device=dev), torch.ones(co, device=dev)
-            beta = zeros if layer.bias is None else layer.bias.detach().to(torch.float32).contiguous()
-            nbytes = lib.sdetr_backbone_packed_bytes(co, ci, k, precision)
-            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=dev)
-            bias = torch.empty(co, dtype=torch.float32, device=dev)
-            _hip.launch("sdetr_backbone_pack", lib, dev, w32.data_ptr(), ones.data_ptr(), beta.data_ptr(), zeros.data_ptr(),
-                        ones.data_ptr(), 0.0, co, ci, k, layout, precision, packed.data_ptr(), bias.data_ptr(),
-                        what="SwinBackbone (pack)")
-            return packed, bias
-        return derived(layer, "swin_packed", (w, layer.bias), build, extra=(precision, self.compute_dtype, layout))
-
-    def _affine(self, norm: nn.LayerNorm) -> Tuple[Tensor, Tensor]:
-        def build():
-            return (norm.weight.detach().to(torch.float32).contiguous(), norm.bias.detach().to(torch.float32).contiguous())
-        return derived(norm, "swin_affine", (norm.weight, norm.bias), build)
 
     def _attention_operands(self, attn: ShiftedWindowAttention) -> Tuple[Tensor, Tensor]:
         """``(bias [heads, N, N], qkv bias [3 C])`` in fp32: the table expanded through the index buffer."""
@@ -393,24 +316,9 @@ class SwinBackbone(nn.Module):
         ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op.
         The buffers of a stage are shared by its blocks (the launches of a plan run in order on one stream)."""
         act = self.compute_dtype if self._precision() == 1 else torch.float32
-        dev, batch = x.device, x.shape[0]
-        ops: List[_hip.SwinOpStruct] = []
-        names: List[str] = []
-        keep: List[Tensor] = [x]
-        outputs: Dict[str, Tensor] = {}
-
-        def new(shape, dtype):
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def op(name, kind, **kw):
-            f = dict(kind=kind, x=None, weight=None, bias=None, gamma=None, beta=None, residual=None, table=None, out=None,
-                     out_nchw=None, batch=batch, in_channels=0, height=1, width=1, out_channels=0, kernel_size=1, stride=1,
-                     x_nchw=0, out_f32=0, window=0, shift=0, heads=0, splits=splits, eps=0.0)
-            f.update(kw)
-            ops.append(_hip.SwinOpStruct(**f))
-            names.append(name)
+        batch = x.shape[0]
+        pb = PlanBuilder(_hip.SwinOpStruct, x, batch=batch, height=1, width=1, kernel_size=1, stride=1, splits=splits)
+        new, op, keep, outputs = pb.new, pb.op, pb.keep, pb.outputs
 
         def gemm(name, kind, layer, src, out, h, w, layout=0, residual=None, nchw=None):
             packed, bias = self._packed(layer, layout)
@@ -421,10 +329,7 @@ class SwinBackbone(nn.Module):
                out_channels=bias.numel(), kernel_size=k, stride=k, x_nchw=layout)
 
         def layer_norm(name, norm, src, out, h, w, c, out_f32=False):
-            gamma, beta = self._affine(norm)
-            keep.extend((gamma, beta))
-            op(name, 3, x=src.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=out.data_ptr(), in_channels=c,
-               height=h, width=w, out_channels=c, out_f32=1 if out_f32 else 0, eps=float(norm.eps))
+            pb.layer_norm(name, 3, self._affine(norm), norm.eps, src, out, h, w, c, out_f32)
 
         stem = self.body.features[0]
         patch, c = stem[0].kernel_size[0], stem[0].out_channels
@@ -471,7 +376,7 @@ class SwinBackbone(nn.Module):
                 gemm(prefix + ".reduction", 0, merging.reduction, gathered, stream, ho, wo)
                 h, w, c = ho, wo, 2 * c
         outputs = {f"features.{2 * i + 1}": outputs[f"features.{2 * i + 1}"] for i in self.return_indices}
-        return ops, outputs, keep, names
+        return pb.ops, outputs, keep, pb.names
 
     def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
         if x.dtype != torch.float32:
@@ -484,12 +389,5 @@ class SwinBackbone(nn.Module):
         if not self.hip_form():
             raise RuntimeError("SwinBackbone: this configuration has no HIP form (window 7 / 12, head dimension 32)")
         ops, outputs, keep, _ = self.build_plan(x, splits)
-        lib, precision = self._lib(), self._precision()
-        arr = (_hip.SwinOpStruct * len(ops))(*ops)
-        ws_bytes = lib.sdetr_swin_workspace_bytes(arr, len(ops), precision)
-        if ws_bytes < 0:
-            _hip.check(-1, "SwinBackbone (workspace)", lib)
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=x.device)
-        _hip.launch("sdetr_swin_run", lib, x.device, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
-                    what="SwinBackbone (run)")
+        self._run_plan(_hip.SwinOpStruct, "sdetr_swin", ops, x.device)
         return outputs

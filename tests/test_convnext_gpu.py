@@ -98,7 +98,7 @@ def test_depthwise_layer_norm_contract(C, hw, window, dtype):
 
 
 @pytest.mark.parametrize("dtype,out_f32", [(torch.float32, 0), (torch.bfloat16, 0), (torch.bfloat16, 1), (torch.float16, 0)])
-@pytest.mark.parametrize("C", [96, 384, 1536])
+@pytest.mark.parametrize("C", [32, 96, 384, 1536, 3072])     # 32: 8 lanes own a quad; 3072: all 12 quads of every lane
 def test_layer_norm_contract(C, dtype, out_f32):
     precision, rounding = ACT[dtype]
     lib = _hip.lib(dtype if dtype == torch.float16 else None)

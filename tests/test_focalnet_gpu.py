@@ -210,7 +210,7 @@ def test_h_with_the_product_epilogue_contract(C, splits, out_f32, dtype):
 
 @pytest.mark.parametrize("dtype,out_f32,copy", [(torch.float32, 1, 0), (torch.bfloat16, 1, 1), (torch.bfloat16, 1, 0),
                                                 (torch.float16, 1, 1), (torch.bfloat16, 0, 0), (torch.float16, 0, 0)])
-@pytest.mark.parametrize("C", [96, 384, 1536])
+@pytest.mark.parametrize("C", [32, 96, 384, 1536, 3072])     # 32: 8 lanes own a quad; 3072: all 12 quads of every lane
 def test_layer_norm_scale_residual_contract(C, dtype, out_f32, copy):
     precision, rounding = ACT[dtype]
     lib = _lib(dtype)

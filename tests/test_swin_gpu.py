@@ -208,7 +208,7 @@ def test_patch_merging_contract(C, hw, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("C", [96, 1536])
+@pytest.mark.parametrize("C", [32, 96, 1536, 3072])          # 32: 8 lanes own a quad; 3072: all 12 quads of every lane
 def test_layer_norm_contract(C, dtype):
     precision, rounding = ACT[dtype]
     g = torch.Generator().manual_seed(C)
