@@ -1394,6 +1394,13 @@ int sdetr_backbone_bwd_run(sdetr_stream_t stream, const sdetr_backbone_bwd_op *o
  * workspace (no atomics: bit-identical from run to run).  Every launch writes every element of its output.
  * sdetr_convnext_op_run runs one op; sdetr_convnext_run a whole plan in order, validated before the first launch;
  * the workspace must hold sdetr_convnext_workspace_bytes (the largest split buffer of the plan).  Tensors 16-byte aligned.
+ *
+ * What a training forward stores for the backward (the two last fields; NULL = the eval launch, bit for bit):
+ *   aux        kind 2: f32 [batch, height, width, C], the depthwise output + bias BEFORE the LayerNorm (the backward
+ *              recomputes the row statistics from it); kind 1: [batch, Ho, Wo, out_channels] in the compute dtype, the
+ *              values acc + bias BEFORE the GELU.  Every element written.  Other kinds: must be NULL.
+ *   row_scale  kind 0: f32 [batch], out = (acc + bias) * row_scale[n] (+ residual): a block's stochastic-depth factor.
+ *              Other kinds: must be NULL.
  * --------------------------------------------------------------------------------------------- */
 typedef struct sdetr_convnext_op {
     int kind;
@@ -1416,6 +1423,8 @@ typedef struct sdetr_convnext_op {
     int out_f32;
     int splits;
     float eps;
+    void *aux;
+    const float *row_scale;
 } sdetr_convnext_op;
 
 int sdetr_convnext_dw_tile(int channels, int *tile_height, int *chunk_channels, int *strip_width);
@@ -1424,6 +1433,75 @@ int sdetr_convnext_op_run(sdetr_stream_t stream, const sdetr_convnext_op *op, in
                           int64_t workspace_bytes);
 int sdetr_convnext_run(sdetr_stream_t stream, const sdetr_convnext_op *ops, int n_ops, int precision, void *workspace,
                        int64_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * ConvNeXt backward (training the ConvNeXt, csrc/convnext_backward.hip): the gradients of the ops above for a block
+ * y = x + s[n] * g (.) (W2 gelu(W1 LN(dw(x) + bd) + b1) + b2) and a down-sampler Conv2d(k = 2, s = 2)(LayerNorm2d(y)).
+ * The residual-stream gradient is channels-last f32 [batch, H, W, C] in BOTH precisions; only the GEMM operands take the
+ * compute dtype (precision 0: f32, 1: the library's 16-bit type).  Parameter gradients are f32.  "rows" are pixels
+ * m = (n * H + y) * W + x, rows = batch * height * width.  No atomics anywhere: a column sum or a tap sum is split into
+ * strips whose partial sums go through the workspace and are added in strip order, so two runs are bit-identical.  Every
+ * launch writes every element of its outputs (no memset is ever needed); nothing syncs with the host.
+ *
+ * sdetr_convnext_bwd_op, by kind (C = channels, K = out_channels):
+ *   0 dgrad:    dz [rows, K] and out [rows, C] in the compute dtype; weight = sdetr_backbone_pack_dgrad's planes of the
+ *               Linear's [K, C] weight (kernel 1; gamma = layer_scale folds it).  sdetr_backbone_dgrad's kernel.
+ *   1 wgrad:    out f32 [K, C] = scale[k] * sum over rows of dz[m, k] * x[m, c]; dz [rows, K], x [rows, C] in the compute
+ *               dtype, scale f32 [K].  sdetr_backbone_wgrad's kernel.
+ *   2 rows:     dz f32 [rows, C]; out [rows, C] in the compute dtype = scale[n] * dz (scale f32 [batch], the block's
+ *               stochastic-depth factors, or NULL = 1); dbias (or NULL) f32 [C] = the column sums of scale[n] * dz.
+ *   3 gelu:     out [rows, C] = dz * gelu'(x), the erf form with the forward's fitted erf; dz, x (the stored pre-GELU
+ *               values) and out in the compute dtype; dbias (or NULL) f32 [C] = the column sums of the unrounded products.
+ *   4 layer norm over C (a multiple of 32 up to 3072): dz [rows, C] in the compute dtype = the gradient at the LayerNorm's
+ *               output, x f32 [rows, C] = its input (the statistics are recomputed, mean then variance about it), gamma
+ *               f32 [C], eps; out f32 [rows, C] = the input gradient (+ add, f32 [rows, C], or NULL); dgamma and dbeta
+ *               (both, or both NULL) f32 [C].
+ *   5 depthwise 7x7 backward-weight: dz f32 [rows, C] = the gradient at the depthwise output, x f32 [rows, C] = its
+ *               input; out f32 [49][C], out[ky * 7 + kx][c] = sum over (n, y, x) of dz[n, y, x, c] *
+ *               x[n, y + ky - 3, x + kx - 3, c] (zeros outside); dbias (or NULL) f32 [C] = the column sums of dz.
+ *   6 depthwise 7x7 backward-data: out f32 [rows, C] = sum over taps of dz[n, y + 3 - ky, x + 3 - kx, c] *
+ *               weight[ky * 7 + kx][c] (+ add, f32 [rows, C], the identity branch, or NULL); weight f32 [49][C].
+ *   7 layer scale: x f32 [C, K] = dW' (kind 1 with scale = 1 on the folded Linear), weight f32 [C, K] = W, scale f32 [C]
+ *               = the Linear's bias b, gamma f32 [C] = g, dz f32 [C] = db' (kind 2's dbias); out (or NULL) f32 [C, K] =
+ *               g[c] * dW'[c, :], dbias (or NULL) f32 [C] = g[c] * db'[c], dgamma (or NULL) f32 [C] =
+ *               sum over k of dW'[c, k] * W[c, k] + db'[c] * b[c].  height = width = batch = 1.
+ *   8 patches:  x [batch, height, width, C] -> out [batch, height / 2, width / 2, 4 C], both in the compute dtype, patch
+ *               element (ky * 2 + kx) * C + c (the space-to-depth rows a 2x2 stride-2 conv multiplies).
+ *   9 pixels:   the reverse: dz [batch, height / 2, width / 2, 4 C] -> out [batch, height, width, C], compute dtype; the
+ *               pixels of an odd last row / column, which the conv's floor crops, get exact zeros.
+ *  10 ingest:   dz = the f32 NCHW cotangent [batch, C, height, width] of a returned map; out f32 [rows, C] = dz (+ add,
+ *               f32 [rows, C], or NULL).
+ * splits: 0 = automatic, n > 0 = n pieces of the reduction (clamped): as in sdetr_backbone_bwd_op for kinds 0 / 1, the
+ * row strips of kinds 2 .. 5.  sdetr_convnext_bwd_workspace_bytes: the largest piece buffer of a plan (-1: a bad op).
+ * sdetr_convnext_bwd_op_run runs one op; sdetr_convnext_bwd_run a whole plan in order, validated before the first launch.
+ * Tensors 16-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_convnext_bwd_op {
+    int kind;
+    const void *dz;
+    const void *x;
+    const void *weight;
+    const float *scale;
+    const float *gamma;
+    const float *add;
+    void *out;
+    float *dbias;
+    float *dgamma;
+    float *dbeta;
+    int batch;
+    int channels;
+    int height;
+    int width;
+    int out_channels;
+    int splits;
+    float eps;
+} sdetr_convnext_bwd_op;
+
+int64_t sdetr_convnext_bwd_workspace_bytes(const sdetr_convnext_bwd_op *ops, int n_ops, int precision);
+int sdetr_convnext_bwd_op_run(sdetr_stream_t stream, const sdetr_convnext_bwd_op *op, int precision, void *workspace,
+                              int64_t workspace_bytes);
+int sdetr_convnext_bwd_run(sdetr_stream_t stream, const sdetr_convnext_bwd_op *ops, int n_ops, int precision,
+                           void *workspace, int64_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * FocalNet backbone (models/backbones/focalnet.py), eval mode, csrc/focalnet.hip.

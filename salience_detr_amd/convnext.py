@@ -19,10 +19,20 @@ How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/
   * the residual stream is channels-last fp32 in every mode; ``set_dtype(bfloat16 | float16)`` takes one 16-bit product
     with fp32 accumulation and keeps the GEMM A operands (normalised rows, the hidden rows) in that type, ``float32``
     (default) multiplies at fp32 accuracy (exact three-way bf16 split of both operands).
-A call with grad enabled on something that requires grad takes the plain-torch composite (``F.conv2d``,
-``F.layer_norm``, ``F.linear``, ``F.gelu``, row-mode stochastic depth), which is the autograd path; ConvNeXt backward in
-HIP is out of scope.  A CPU tensor on the HIP form raises: the hot path has no CPU fallback.
+By default a call with grad enabled on something that requires grad takes the plain-torch composite (``F.conv2d``,
+``F.layer_norm``, ``F.linear``, ``F.gelu``, row-mode stochastic depth), which is the default autograd path.  A CPU tensor
+on the HIP form raises: the hot path has no CPU fallback.
+
+Training in HIP (``set_train_form("hip")``, ``csrc/convnext_backward.hip``): a forward that needs autograd runs the same
+plan inside one autograd node, with three additions to its launches (``aux`` / ``row_scale`` of ``sdetr_convnext_op``):
+the depthwise launch also stores its fp32 values before the LayerNorm, Linear 1 its values before the GELU, and Linear 2
+multiplies by the block's stochastic-depth factor per sample (drawn on the device exactly as ``StochasticDepth`` draws
+it).  The backward is one ``sdetr_convnext_bwd_run`` call over ``_backward_ops``: it stops below the lowest trainable
+module and returns fp32 gradients for the parameters that require them.  Served: ``hip_form()`` with a frozen stem, an
+input without gradient, float32 or bfloat16.  The stem's backward, a gradient to the image and float16 training are out
+of scope; anything else raises at forward.
 """
+import weakref
 from functools import partial
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -162,6 +172,7 @@ class ConvNeXtBackbone(HipBackbone):
         self.features = net.features
         self.num_channels = [self.block_setting[i].input_channels for i in self.return_indices]
         self.compute_dtype = torch.float32
+        self.train_form = "torch"
         if weights is not None:
             self.load_weights(weights)
         if len(freeze_indices) > 0:
@@ -205,22 +216,33 @@ class ConvNeXtBackbone(HipBackbone):
                     conv.bias.detach().to(torch.float32).contiguous())
         return derived(conv, "convnext_taps", (conv.weight, conv.bias), build)
 
-    def build_plan(self, x: Tensor, splits: int = 0):
+    def build_plan(self, x: Tensor, splits: int = 0, train: Optional[dict] = None):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
-        ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op."""
+        ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op.
+        ``train`` (a dict with ``"first"``, the index in ``_sequence()`` of the lowest module whose backward will run):
+        a training forward; it receives ``"acts"`` (what the backward reads, by op name) and ``"factors"`` (the
+        stochastic-depth factors ``[B]`` of every block that drew some, by block name)."""
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
         batch = x.shape[0]
         pb = PlanBuilder(_hip.ConvnextOpStruct, x, batch=batch, kernel_size=1, stride=1)
         new, keep, outputs = pb.new, pb.keep, pb.outputs
 
-        def gemm(name, kind, layer, src, h, w, ci, k, scale=None, residual=None, nchw=None, x_nchw=False):
+        acts: Dict[str, Tensor] = {}
+        factors: Dict[str, Tensor] = {}
+        if train is not None:
+            train["acts"], train["factors"] = acts, factors
+        index = 0   # of the current module in _sequence()
+
+        def gemm(name, kind, layer, src, h, w, ci, k, scale=None, residual=None, nchw=None, x_nchw=False, aux=None,
+                 row_scale=None):
             packed, bias = self._packed(layer, 1 if x_nchw else 0, scale)
             keep.extend((packed, bias))
             co, ho, wo = layer.weight.shape[0], (h - k) // k + 1, (w - k) // k + 1
             out = new((batch, ho, wo, co), act if kind == 1 else torch.float32)
             pb.op(name, kind, x=src.data_ptr(), weight=packed.data_ptr(), bias=bias.data_ptr(), residual=_hip.ptr(residual),
                   out=out.data_ptr(), out_nchw=_hip.ptr(nchw), in_channels=ci, height=h, width=w, out_channels=co,
-                  kernel_size=k, stride=k, x_nchw=1 if x_nchw else 0, splits=splits)
+                  kernel_size=k, stride=k, x_nchw=1 if x_nchw else 0, splits=splits, aux=_hip.ptr(aux),
+                  row_scale=_hip.ptr(row_scale))
             return out, ho, wo
 
         def layer_norm(name, norm, src, h, w, c, out_f32):
@@ -241,24 +263,42 @@ class ConvNeXtBackbone(HipBackbone):
                 gamma, beta = self._affine(norm)
                 keep.extend((taps, dw_bias, gamma, beta))
                 rows = new((batch, h, w, c), act)
+                stored = train is not None and index >= train["first"]
+                pre_norm = new((batch, h, w, c), torch.float32) if stored else None
+                pre_gelu = new((batch, h, w, 4 * c), act) if stored else None
+                factor = None
+                sd = blk.stochastic_depth
+                if train is not None and sd.training and sd.p > 0.0:   # StochasticDepth.forward's own draw, in its order
+                    factor = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=x.device).bernoulli_(1.0 - sd.p)
+                    if sd.p < 1.0:
+                        factor.div_(1.0 - sd.p)
+                    keep.append(factor)
+                    factors[prefix] = factor.view(batch)
                 pb.op(prefix + ".block.0+2", 2, x=y.data_ptr(), weight=taps.data_ptr(), bias=dw_bias.data_ptr(),
                       gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=rows.data_ptr(), in_channels=c, height=h, width=w,
-                      out_channels=c, kernel_size=7, eps=float(norm.eps))
-                hidden, _, _ = gemm(prefix + ".block.3", 1, fc1, rows, h, w, c, 1)
+                      out_channels=c, kernel_size=7, eps=float(norm.eps), aux=_hip.ptr(pre_norm))
+                hidden, _, _ = gemm(prefix + ".block.3", 1, fc1, rows, h, w, c, 1, aux=pre_gelu)
                 nchw = None
                 if i in self.return_indices and j == len(stage) - 1:
                     nchw = new((batch, c, h, w), torch.float32)
                     outputs[f"features.{2 * i + 1}"] = nchw
+                if stored:
+                    acts.update({prefix + ".in": y, prefix + ".block.0": pre_norm, prefix + ".block.2": rows,
+                                 prefix + ".block.3": pre_gelu, prefix + ".block.4": hidden})
                 y, _, _ = gemm(prefix + ".block.5", 0, fc2, hidden, h, w, 4 * c, 1, scale=blk.layer_scale, residual=y,
-                               nchw=nchw)
+                               nchw=nchw, row_scale=factor)
+                index += 1
             if i < self.num_stages - 1:
                 down = self.features[2 * i + 2]
                 t = layer_norm(f"features.{2 * i + 2}.0", down[0], y, h, w, c, False)
+                if train is not None and index >= train["first"]:
+                    acts.update({f"features.{2 * i + 2}.in": y, f"features.{2 * i + 2}.0": t})
                 y, h, w = gemm(f"features.{2 * i + 2}.1", 0, down[1], t, h, w, c, 2)
                 c = down[1].weight.shape[0]
+                index += 1
         return pb.ops, outputs, keep, pb.names
 
-    def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+    def forward_hip(self, x: Tensor, splits: int = 0, train: Optional[dict] = None) -> Dict[str, Tensor]:
         if x.dtype != torch.float32:
             x = x.float()
         _hip.require_device("ConvNeXtBackbone", x=x)
@@ -268,6 +308,329 @@ class ConvNeXtBackbone(HipBackbone):
             raise RuntimeError(f"ConvNeXtBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
         if min(x.shape[2], x.shape[3]) < 4 * 2 ** (self.num_stages - 1):
             raise RuntimeError(f"ConvNeXtBackbone: a {tuple(x.shape[2:])} canvas leaves a stage without pixels")
-        ops, outputs, keep, _ = self.build_plan(x, splits)
+        ops, outputs, keep, _ = self.build_plan(x, splits, train)
         self._run_plan(_hip.ConvnextOpStruct, "sdetr_convnext", ops, x.device)
         return outputs
+
+    # ------------------------------------------------------------------------------------------ training in HIP
+    def forward(self, x: Tensor) -> Dict[str, Tensor]:
+        if self.train_form == "hip" and self._needs_autograd(x):
+            return self.forward_hip_train(x)
+        return super().forward(x)
+
+    def set_train_form(self, form: str):
+        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
+        (the HIP forward plan inside an autograd node whose backward is one ``sdetr_convnext_bwd_run`` call, see
+        ``forward_hip_train``).  ``"hip"`` on a module or input that is not eligible (``hip_train_reason``) raises at
+        forward: it never falls back."""
+        if form not in ("torch", "hip"):
+            raise ValueError(f"ConvNeXtBackbone.set_train_form: {form!r} is not 'torch' / 'hip'")
+        self.train_form = form
+        return self
+
+    def hip_train_reason(self, x: Optional[Tensor] = None) -> Optional[str]:
+        """Why the ``"hip"`` training form cannot serve this module (and input ``x``); ``None`` when it can."""
+        if not self.hip_form():
+            return "the architecture is not one the HIP kernels serve (a block other than CNBlock with nn.LayerNorm, a " \
+                   "norm other than LayerNorm2d, or a width that is no multiple of 32 up to 3072)"
+        if any(p.requires_grad for p in self.features[0].parameters()):
+            return "the stem (features.0) is not frozen: the 4x4 patchify backward is out of scope"
+        if self.compute_dtype not in (torch.float32, torch.bfloat16):
+            return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
+        if x is not None and x.requires_grad:
+            return "the input requires a gradient: the gradient to the image is out of scope"
+        return None
+
+    def hip_train_form(self, x: Optional[Tensor] = None) -> bool:
+        """True when ``set_train_form("hip")`` can train this module (on input ``x``): ``hip_form()``, a frozen stem, an
+        input without gradient and a float32 / bfloat16 compute dtype."""
+        return self.hip_train_reason(x) is None
+
+    def _sequence(self) -> List[Tuple[str, str, nn.Module]]:
+        """``(kind, name, module)`` of every block (``"block"``) and down-sampler (``"down"``) in forward order."""
+        seq = []
+        for i, stage in enumerate(self.stages()):
+            seq.extend(("block", f"features.{2 * i + 1}.{j}", blk) for j, blk in enumerate(stage))
+            if i < self.num_stages - 1:
+                seq.append(("down", f"features.{2 * i + 2}", self.features[2 * i + 2]))
+        return seq
+
+    def _first_trainable(self) -> Optional[int]:
+        """The index in ``_sequence()`` of the lowest module with a trainable parameter: where the backward stops."""
+        for idx, (_, _, m) in enumerate(self._sequence()):
+            if any(p.requires_grad for p in m.parameters()):
+                return idx
+        return None
+
+    def _trainable(self) -> List[Tuple[str, nn.Parameter]]:
+        return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+
+    def forward_hip_train(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+        """The ``"hip"`` training form: the HIP forward plan as one autograd node.  The node keeps the activations the
+        backward reads (no copy); its backward is one ``sdetr_convnext_bwd_run`` call and returns the fp32 parameter
+        gradients to autograd, which accumulates them into ``.grad``."""
+        reason = self.hip_train_reason(x)
+        if reason is not None:
+            raise RuntimeError(f"ConvNeXtBackbone: the 'hip' training form cannot run: {reason}")
+        named = self._trainable()
+        maps = _ConvNeXtTrainFunction.apply(self, x, splits, tuple(n for n, _ in named), *[p for _, p in named])
+        return dict(zip([f"features.{2 * i + 1}" for i in sorted(self.return_indices)], maps))
+
+    def _train_state(self) -> dict:
+        state = self.__dict__.get("_train_state_ref")
+        state = state() if state is not None else None
+        if state is None:
+            raise RuntimeError("ConvNeXtBackbone: no 'hip' training forward is alive")
+        return state
+
+    def saved_activations(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): what the last ``"hip"`` training forward stored, by op name: ``<block>.in`` (the block's
+        fp32 input rows), ``<block>.block.0`` (fp32, before the LayerNorm), ``.block.2`` (normalised rows), ``.block.3``
+        (before the GELU), ``.block.4`` (after it), and ``<down>.in`` / ``<down>.0`` of a down-sampler.  Valid while that
+        forward's autograd graph is alive."""
+        return dict(self._train_state()["acts"])
+
+    def stochastic_depth_factors(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): ``{block name: factors [B]}`` (0 or 1 / (1 - p)) the last ``"hip"`` training forward
+        drew, in forward order; blocks with ``p == 0`` or in ``eval()`` draw nothing.  Valid as ``saved_activations``."""
+        return dict(self._train_state()["factors"])
+
+    def _packed_dgrad(self, layer: nn.Module, scale: Optional[Tensor] = None) -> Tensor:
+        """The backward-data planes (``sdetr_backbone_pack_dgrad``, kernel 1) of a Linear's ``[out, in]`` weight, ``scale``
+        (the layer scale) folded per output; of the 2x2 down-sampler conv, its weight as ``[out, (ky, kx, in)]`` rows."""
+        precision, lib = self._precision(), self._lib()
+        w = layer.weight
+
+        def build():
+            w32 = w.detach().to(torch.float32)
+            if w32.dim() == 4:
+                w32 = w32.permute(0, 2, 3, 1)
+            w32 = w32.reshape(w.shape[0], -1).contiguous()
+            co, ci = w32.shape
+            gamma = torch.ones(co, device=w.device) if scale is None else scale.detach().to(torch.float32).reshape(co).contiguous()
+            ones = torch.ones(co, device=w.device)
+            packed = torch.empty(lib.sdetr_backbone_dgrad_packed_bytes(co, ci, 1, precision) // 2, dtype=torch.int16,
+                                 device=w.device)
+            unused = torch.empty(co, dtype=torch.float32, device=w.device)
+            _hip.launch("sdetr_backbone_pack_dgrad", lib, w.device, w32.data_ptr(), gamma.data_ptr(), ones.data_ptr(), 0.0, co,
+                        ci, 1, precision, packed.data_ptr(), unused.data_ptr(), what="ConvNeXtBackbone (pack dgrad)")
+            return packed
+        return derived(layer, "convnext_packed_dgrad", (w, scale), build, extra=(precision, self.compute_dtype))
+
+    def _f32(self, owner, name: str, t: Tensor) -> Tensor:
+        """A parameter as a contiguous fp32 tensor, cached per version."""
+        return derived(owner, "convnext_f32_" + name, (t,), lambda: t.detach().to(torch.float32).contiguous().clone())
+
+    def _backward_ops(self, acts: Dict[str, Tensor], factors: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]],
+                      splits: int = 0):
+        """The backward of one forward as ``(ops, names, grads, keep)``: ``ops`` the ``sdetr_convnext_bwd_op`` list in run
+        order, ``names`` one label per op, ``grads`` ``{parameter name: fp32 gradient}`` (as views of what the ops write),
+        ``keep`` every tensor the ops point into.  Walks ``_sequence()`` from the top down to the lowest trainable module."""
+        batch, _, height, width = shape
+        seq, first = self._sequence(), self._first_trainable()
+        act = torch.float32 if self._precision() == 0 else self.compute_dtype
+        dev = next(iter(acts.values())).device
+        pb = PlanBuilder(_hip.ConvnextBwdOpStruct, next(iter(acts.values())), batch=batch, splits=splits)
+        new, keep = pb.new, pb.keep
+        scratch: Dict[tuple, Tensor] = {}
+        grads: Dict[str, Tensor] = {}
+
+        def tmp(tag, shape_, dtype):   # a buffer the next block may overwrite: the plan runs in order on one stream
+            key = (tag, tuple(shape_), dtype)
+            if key not in scratch:
+                scratch[key] = new(shape_, dtype)
+            return scratch[key]
+
+        def ones(n):
+            key = ("ones", n)
+            if key not in scratch:
+                scratch[key] = torch.ones(n, device=dev)
+                keep.append(scratch[key])
+            return scratch[key]
+
+        def want(*params):
+            return any(p is not None and p.requires_grad for p in params)
+
+        # the spatial size of every module's input
+        sizes, h, w = [], height // 4, width // 4
+        for kind, _, _ in seq:
+            sizes.append((h, w))
+            if kind == "down":
+                h, w = h // 2, w // 2
+        stage_of = {f"features.{2 * i + 1}.{len(st) - 1}": i for i, st in enumerate(self.stages())}
+
+        dy, flip = None, 0
+        for idx in range(len(seq) - 1, first - 1, -1):
+            kind, name, m = seq[idx]
+            h, w = sizes[idx]
+            below = idx > first
+            if kind == "block":
+                c = m.block[0].weight.shape[0]
+                stage = stage_of.get(name)
+                if stage is not None and stage in self.return_indices:
+                    g = cotangents.get(f"features.{2 * stage + 1}")
+                    if g is not None or dy is None:
+                        g = torch.zeros((batch, c, h, w), device=dev) if g is None else g.to(torch.float32).contiguous()
+                        keep.append(g)
+                        out = new((batch, h, w, c), torch.float32)
+                        pb.op(name + " (ingest)", 10, dz=g.data_ptr(), add=_hip.ptr(dy), out=out.data_ptr(), channels=c, height=h,
+                              width=w)
+                        dy = out
+                dw, norm, fc1, fc2 = m.block[0], m.block[2], m.block[3], m.block[5]
+                factor = factors.get(name)
+                dzs, db2p = tmp("dzs", (batch, h, w, c), act), tmp("db2p", (c,), torch.float32)
+                pb.op(name + " (rows)", 2, dz=dy.data_ptr(), scale=_hip.ptr(factor), out=dzs.data_ptr(), dbias=db2p.data_ptr(),
+                      channels=c, height=h, width=w)
+                if want(fc2.weight, fc2.bias, m.layer_scale):
+                    dw2p = tmp("dw2p", (c, 4 * c), torch.float32)
+                    pb.op(name + ".block.5 (wgrad)", 1, dz=dzs.data_ptr(), x=acts[name + ".block.4"].data_ptr(),
+                          scale=ones(c).data_ptr(), out=dw2p.data_ptr(), channels=4 * c, height=h, width=w, out_channels=c)
+                    dw2 = new((c, 4 * c), torch.float32) if want(fc2.weight) else None
+                    db2 = new((c,), torch.float32) if want(fc2.bias) else None
+                    dg = new((c,), torch.float32) if want(m.layer_scale) else None
+                    w2, b2 = self._f32(fc2, "weight", fc2.weight), self._f32(fc2, "bias", fc2.bias)
+                    g32 = self._f32(m, "layer_scale", m.layer_scale)
+                    keep.extend((w2, b2, g32))
+                    pb.op(name + " (layer scale)", 7, dz=db2p.data_ptr(), x=dw2p.data_ptr(), weight=w2.data_ptr(),
+                          scale=b2.data_ptr(), gamma=g32.data_ptr(), out=_hip.ptr(dw2), dbias=_hip.ptr(db2), dgamma=_hip.ptr(dg),
+                          batch=1, channels=c, height=1, width=1, out_channels=4 * c)
+                    for pname, t in ((".block.5.weight", dw2), (".block.5.bias", db2)):
+                        if t is not None:
+                            grads[name + pname] = t
+                    if dg is not None:
+                        grads[name + ".layer_scale"] = dg.view(c, 1, 1)
+                if not (below or want(dw.weight, dw.bias, norm.weight, norm.bias, fc1.weight, fc1.bias)):
+                    continue
+                packed2 = self._packed_dgrad(fc2, m.layer_scale)
+                dh = tmp("dh", (batch, h, w, 4 * c), act)
+                pb.op(name + ".block.5 (dgrad)", 0, dz=dzs.data_ptr(), weight=packed2.data_ptr(), out=dh.data_ptr(),
+                      channels=4 * c, height=h, width=w, out_channels=c)
+                db1 = new((4 * c,), torch.float32) if want(fc1.bias) else None
+                pb.op(name + ".block.4 (gelu)", 3, dz=dh.data_ptr(), x=acts[name + ".block.3"].data_ptr(), out=dh.data_ptr(),
+                      dbias=_hip.ptr(db1), channels=4 * c, height=h, width=w)
+                if db1 is not None:
+                    grads[name + ".block.3.bias"] = db1
+                if want(fc1.weight):
+                    dw1 = new((4 * c, c), torch.float32)
+                    pb.op(name + ".block.3 (wgrad)", 1, dz=dh.data_ptr(), x=acts[name + ".block.2"].data_ptr(),
+                          scale=ones(4 * c).data_ptr(), out=dw1.data_ptr(), channels=c, height=h, width=w, out_channels=4 * c)
+                    grads[name + ".block.3.weight"] = dw1
+                keep.append(packed2)
+                if not (below or want(dw.weight, dw.bias, norm.weight, norm.bias)):
+                    continue
+                packed1 = self._packed_dgrad(fc1)
+                keep.append(packed1)
+                dn = tmp("dn", (batch, h, w, c), act)
+                pb.op(name + ".block.3 (dgrad)", 0, dz=dh.data_ptr(), weight=packed1.data_ptr(), out=dn.data_ptr(), channels=c,
+                      height=h, width=w, out_channels=4 * c)
+                d = tmp("d", (batch, h, w, c), torch.float32)
+                gamma = self._f32(norm, "weight", norm.weight)
+                keep.append(gamma)
+                affine = want(norm.weight, norm.bias)
+                dgam = new((c,), torch.float32) if affine else None
+                dbet = new((c,), torch.float32) if affine else None
+                pb.op(name + ".block.2 (layer norm)", 4, dz=dn.data_ptr(), x=acts[name + ".block.0"].data_ptr(),
+                      gamma=gamma.data_ptr(), out=d.data_ptr(), dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), channels=c, height=h,
+                      width=w, eps=float(norm.eps))
+                if want(norm.weight):
+                    grads[name + ".block.2.weight"] = dgam
+                if want(norm.bias):
+                    grads[name + ".block.2.bias"] = dbet
+                if want(dw.weight, dw.bias):
+                    dtaps = new((49, c), torch.float32)
+                    dbd = new((c,), torch.float32) if want(dw.bias) else None
+                    pb.op(name + ".block.0 (wgrad)", 5, dz=d.data_ptr(), x=acts[name + ".in"].data_ptr(), out=dtaps.data_ptr(),
+                          dbias=_hip.ptr(dbd), channels=c, height=h, width=w)
+                    if want(dw.weight):
+                        grads[name + ".block.0.weight"] = dtaps.t().reshape(c, 1, 7, 7)
+                    if dbd is not None:
+                        grads[name + ".block.0.bias"] = dbd
+                if below:
+                    taps, _ = self._taps(dw)
+                    keep.append(taps)
+                    dx = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
+                    flip ^= 1
+                    pb.op(name + ".block.0 (dgrad)", 6, dz=d.data_ptr(), weight=taps.data_ptr(), add=dy.data_ptr(),
+                          out=dx.data_ptr(), channels=c, height=h, width=w)
+                    dy = dx
+            else:
+                norm, conv = m[0], m[1]
+                c, co = conv.weight.shape[1], conv.weight.shape[0]
+                ho, wo = h // 2, w // 2
+                dzc = tmp("dzc", (batch, ho, wo, co), act)
+                dbc = new((co,), torch.float32) if want(conv.bias) else None
+                pb.op(name + ".1 (rows)", 2, dz=dy.data_ptr(), out=dzc.data_ptr(), dbias=_hip.ptr(dbc), channels=co, height=ho,
+                      width=wo)
+                if dbc is not None:
+                    grads[name + ".1.bias"] = dbc
+                if want(conv.weight):
+                    patches = tmp("patches", (batch, ho, wo, 4 * c), act)
+                    pb.op(name + ".1 (patches)", 8, x=acts[name + ".0"].data_ptr(), out=patches.data_ptr(), channels=c, height=h,
+                          width=w)
+                    dwp = new((co, 4 * c), torch.float32)
+                    pb.op(name + ".1 (wgrad)", 1, dz=dzc.data_ptr(), x=patches.data_ptr(), scale=ones(co).data_ptr(),
+                          out=dwp.data_ptr(), channels=4 * c, height=ho, width=wo, out_channels=co)
+                    grads[name + ".1.weight"] = dwp.view(co, 2, 2, c).permute(0, 3, 1, 2)
+                dy_next = None
+                if below or want(norm.weight, norm.bias):
+                    packed = self._packed_dgrad(conv)
+                    keep.append(packed)
+                    dpatch = tmp("dpatch", (batch, ho, wo, 4 * c), act)
+                    pb.op(name + ".1 (dgrad)", 0, dz=dzc.data_ptr(), weight=packed.data_ptr(), out=dpatch.data_ptr(),
+                          channels=4 * c, height=ho, width=wo, out_channels=co)
+                    dn = tmp("dn", (batch, h, w, c), act)
+                    pb.op(name + ".1 (pixels)", 9, dz=dpatch.data_ptr(), out=dn.data_ptr(), channels=c, height=h, width=w)
+                    gamma = self._f32(norm, "weight", norm.weight)
+                    keep.append(gamma)
+                    affine = want(norm.weight, norm.bias)
+                    dgam = new((c,), torch.float32) if affine else None
+                    dbet = new((c,), torch.float32) if affine else None
+                    dy_next = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
+                    flip ^= 1
+                    pb.op(name + ".0 (layer norm)", 4, dz=dn.data_ptr(), x=acts[name + ".in"].data_ptr(), gamma=gamma.data_ptr(),
+                          out=dy_next.data_ptr(), dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), channels=c, height=h, width=w,
+                          eps=float(norm.eps))
+                    if want(norm.weight):
+                        grads[name + ".0.weight"] = dgam
+                    if want(norm.bias):
+                        grads[name + ".0.bias"] = dbet
+                dy = dy_next
+        return pb.ops, pb.names, grads, keep
+
+    def _run_backward(self, acts: Dict[str, Tensor], factors: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]],
+                      splits: int = 0) -> Dict[str, Tensor]:
+        """Runs the backward plan on the stored activations; returns ``{parameter name: fp32 gradient}``."""
+        ops, _, grads, keep = self._backward_ops(acts, factors, shape, cotangents, splits)
+        if ops:
+            dev = next(iter(acts.values())).device
+            self._run_plan(_hip.ConvnextBwdOpStruct, "sdetr_convnext_bwd", ops, dev)
+        return grads
+
+
+class _TrainState(dict):
+    """A dict that can be weakly referenced (``ConvNeXtBackbone.saved_activations``)."""
+
+
+class _ConvNeXtTrainFunction(torch.autograd.Function):
+    """``ConvNeXtBackbone.forward_hip_train``: inputs are the trainable parameters, outputs the returned fp32 maps."""
+
+    @staticmethod
+    def forward(ctx, backbone: "ConvNeXtBackbone", x: Tensor, splits: int, names: Tuple[str, ...], *params: Tensor):
+        state = _TrainState(first=backbone._first_trainable())
+        outputs = backbone.forward_hip(x, splits, state)
+        ctx.backbone, ctx.state, ctx.names, ctx.splits = backbone, state, names, splits
+        ctx.shape = tuple(x.shape)
+        ctx.keys = sorted(outputs)
+        backbone.__dict__["_train_state_ref"] = weakref.ref(state)
+        return tuple(outputs[k] for k in ctx.keys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        state = ctx.state
+        dws = ctx.backbone._run_backward(state["acts"], state["factors"], ctx.shape, dict(zip(ctx.keys, grads)), ctx.splits)
+        out = []
+        for n in ctx.names:
+            g = dws.get(n)
+            out.append(None if g is None else g.contiguous())
+        return (None, None, None, None) + tuple(out)

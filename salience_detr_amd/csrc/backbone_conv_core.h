@@ -28,8 +28,9 @@ struct BConv {
     uint32_t x_bytes, w_bytes;
     int batch, ci, h, w_in, co, ks, stride, pad, ho, wo, M, K, kpad, relu, splits, k_per_split;
     int64_t plane;          // co * kpad
-    const float *q;         // EPI 3 / 4: the fp32 multiplier rows, element (m, co) at q[m * ldq + co]
+    const float *q;         // EPI 3 / 4: the fp32 multiplier rows, element (m, co) at q[m * ldq + co]; EPI 7: q[n]
     int ldq;
+    char *aux;              // EPI 6: the pre-GELU values [M][co], compute dtype
 };
 
 // where output pixel m reads its taps: input row / column of tap (0, 0) and the image's first element
@@ -152,12 +153,22 @@ struct BLoadW {
 //   3  (v + b[co]) * q[m][co] -> out (rows, compute dtype): FocalNet's h with the modulation product (focalnet.hip)
 //   4  the same product -> out (fp32 rows in every precision): h in front of the modulation's own LayerNorm
 //   5  v + b[co] -> out (rows, compute dtype): Swin's qkv (swin.hip)
+//   6  EPI 1 that also stores v + b[co] -> aux (rows, compute dtype): what a ConvNeXt training forward keeps
+//   7  EPI 2 with (v + b[co]) * q[n] before the residual: a ConvNeXt block under stochastic depth (q per sample)
 template <bool X3, int EPI>
 __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
 {
     v += c.bias[co];
     const int64_t e = (int64_t)m * c.co + co;
     if (EPI == 1) {
+        v = gelu_erf(v);
+        if (X3) reinterpret_cast<float *>(c.out)[e] = v;
+        else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
+        return;
+    }
+    if (EPI == 6) {
+        if (X3) reinterpret_cast<float *>(c.aux)[e] = v;
+        else reinterpret_cast<uint16_t *>(c.aux)[e] = (uint16_t)f32_to_act_bits(v);
         v = gelu_erf(v);
         if (X3) reinterpret_cast<float *>(c.out)[e] = v;
         else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
@@ -174,12 +185,13 @@ __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
         else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
         return;
     }
+    if (EPI == 7) v *= c.q[m / (c.ho * c.wo)];
     if (c.res) {
-        if (X3 || EPI == 2) v += reinterpret_cast<const float *>(c.res)[e];
+        if (X3 || EPI == 2 || EPI == 7) v += reinterpret_cast<const float *>(c.res)[e];
         else v += act_lo(reinterpret_cast<const uint16_t *>(c.res)[e]);
     }
     if (EPI == 0 && c.relu) v = fmaxf(v, 0.f);
-    if (X3 || EPI == 2) reinterpret_cast<float *>(c.out)[e] = v;
+    if (X3 || EPI == 2 || EPI == 7) reinterpret_cast<float *>(c.out)[e] = v;
     else reinterpret_cast<uint16_t *>(c.out)[e] = (uint16_t)f32_to_act_bits(v);
     if (c.out_nchw) {
         const int hw = c.ho * c.wo, n = m / hw, pix = m - n * hw;
@@ -289,7 +301,7 @@ struct ConvGeom {
     int batch, ci, h, w, co, ks, stride, pad, ho, wo, x_nchw, splits;
 };
 
-// c = the kernel's arguments for g: every member set (those a family adds afterwards -- out_nchw, q / ldq, relu -- start
+// c = the kernel's arguments for g: every member set (those a family adds afterwards -- out_nchw, q / ldq, aux, relu -- start
 // null / 0), K padded to whole reduction tiles, the 32-bit size limits, the resolved split of the reduction
 int fill_conv(const char *what, const ConvGeom &g, int precision, BConv &c)
 {

@@ -14,6 +14,8 @@
 //                               its 1x1 case over rows, the down-sampler its 2x2 stride-2 case, the stem its 4x4 stride-4
 //                               case on the fp32 NCHW canvas; epilogue gelu(acc + b) (EPI 1) or acc + b (+ fp32 residual)
 //                               with the fp32 NCHW copy of a returned stage (EPI 2).  Weights: sdetr_backbone_pack.
+// A training forward (convnext_backward.hip is its backward) sets `aux` / `row_scale`: the depthwise launch also writes its
+// pre-norm fp32 values, Linear 1 its pre-GELU values (EPI 6), Linear 2 scales acc + b per sample (EPI 7).  Null: as above.
 // The row LayerNorm, the host checks of a rows op and the plan entry points are backbone_rows_core.h's.
 // No atomics; a split reduction is summed in split order through the workspace.
 #include "backbone_rows_core.h"
@@ -57,6 +59,7 @@ struct CnDw {
     const float *taps;    // [49][C]
     const float *bias, *gamma, *beta;
     char *out;            // [B, H, W, C] compute dtype
+    float *pre_out;       // [B, H, W, C] fp32: the values before the LayerNorm (a training forward), or null
     int batch, h, w, c, th, cc, tiles_x, tiles_y;
     float eps;
 };
@@ -146,6 +149,7 @@ __global__ void __launch_bounds__(kCnThreads) convnext_dwconv_ln_kernel(CnDw a)
         const int64_t o = (((int64_t)n * a.h + py) * a.w + px) * a.c;
         for (int q = lane; q < nq; q += 64) {
             const float4 v = *reinterpret_cast<const float4 *>(r + 4 * q);
+            if (a.pre_out) *reinterpret_cast<float4 *>(a.pre_out + o + 4 * q) = v;
             const float4 g = *reinterpret_cast<const float4 *>(a.gamma + 4 * q);
             const float4 be = *reinterpret_cast<const float4 *>(a.beta + 4 * q);
             const float o0 = fmaf((v.x - mean) * rstd, g.x, be.x), o1 = fmaf((v.y - mean) * rstd, g.y, be.y);
@@ -164,8 +168,10 @@ int make_dw(const sdetr_convnext_op &o, int precision, CnDw &a, CnTile &t)
     if (!o.x || !o.weight || !o.bias || !o.gamma || !o.beta || !o.out) return fail("%s: null tensor", what);
     if (!tile_for(o.in_channels, t))
         return fail("%s: channels must be a multiple of 32 in [32, %d] (got %d)", what, kCnMaxC, o.in_channels);
-    if (!all_aligned16(o.x, o.weight, o.bias, o.gamma, o.beta, o.out))
+    if (!all_aligned16(o.x, o.weight, o.bias, o.gamma, o.beta, o.out, o.aux))
         return fail("%s: tensors must be 16-byte aligned", what);
+    if (o.row_scale) return fail("%s: row_scale belongs to kind 0", what);
+    a.pre_out = reinterpret_cast<float *>(o.aux);
     a.x = reinterpret_cast<const float *>(o.x);
     a.taps = reinterpret_cast<const float *>(o.weight);
     a.bias = o.bias;
@@ -214,6 +220,7 @@ int run_dw(hipStream_t s, const sdetr_convnext_op &o, int precision)
 
 int check_ln(const sdetr_convnext_op &o, int precision)
 {
+    if (o.aux || o.row_scale) return fail("sdetr_convnext (LayerNorm): aux / row_scale belong to kinds 0 .. 2");
     return check_ln_rows("sdetr_convnext (LayerNorm)", o.batch, o.height, o.width, o.in_channels, precision, o.x, o.gamma, o.beta,
                          o.out);
 }
@@ -239,13 +246,17 @@ int make_gemm(const sdetr_convnext_op &o, int precision, BConv &c)
     if (o.x_nchw == 0 && o.in_channels % 32)
         return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
     if (o.kind == 1 && (o.residual || o.out_nchw)) return fail("%s: the GELU epilogue takes no residual / NCHW copy", what);
-    if (!all_aligned16(o.x, o.weight)) return fail("%s: x and weight must be 16-byte aligned", what);
+    if (!all_aligned16(o.x, o.weight, o.aux, o.row_scale)) return fail("%s: x, weight, aux and row_scale must be 16-byte aligned", what);
+    if ((o.kind == 0 && o.aux) || (o.kind == 1 && o.row_scale))
+        return fail("%s: aux belongs to the GELU epilogue (kind 1), row_scale to the linear one (kind 0)", what);
     const int ho = out_hw(o.height, o.kernel_size, o.stride, 0), wo = out_hw(o.width, o.kernel_size, o.stride, 0);
     if (ho < 1 || wo < 1) return fail("%s: empty output", what);
     const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
                         o.kernel_size, o.stride, 0, ho, wo, o.x_nchw, o.splits};
     if (int rc = fill_conv(what, g, precision, c)) return rc;
     c.out_nchw = o.out_nchw;
+    c.aux = reinterpret_cast<char *>(o.aux);
+    c.q = o.row_scale;
     return 0;
 }
 
@@ -257,7 +268,9 @@ int run_gemm(hipStream_t s, const sdetr_convnext_op &o, int precision, void *ws,
         return fail("sdetr_convnext (patchify GEMM): workspace of %lld bytes is too small (%lld needed)",
                     (long long)ws_bytes, (long long)conv_workspace(c));
     c.partial = reinterpret_cast<float *>(ws);
-    if (o.kind == 1) launch_gemm<1>(s, c, precision == 0, o.x_nchw != 0);
+    if (o.kind == 1 && o.aux) launch_gemm<6>(s, c, precision == 0, o.x_nchw != 0);
+    else if (o.kind == 1) launch_gemm<1>(s, c, precision == 0, o.x_nchw != 0);
+    else if (o.row_scale) launch_gemm<7>(s, c, precision == 0, o.x_nchw != 0);
     else launch_gemm<2>(s, c, precision == 0, o.x_nchw != 0);
     return check_launch("sdetr_convnext (patchify GEMM)");
 }
