@@ -103,7 +103,7 @@ def main():
         for dt, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
             m.set_dtype(dt)
             res[f"hip_{tag}_us"] = round(replayed(lambda: m(x), args.warmup, args.iters), 1)
-            ops, _, keep = m.build_plan(x)
+            ops, _, keep, _ = m.build_plan(x)
             lib, prec = m._lib(), m._precision()
             total = 0.0
             for name, a, b in stage_slices(m):

@@ -14,7 +14,8 @@ How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/
     and the ReLU; the weight is folded and packed once per parameter version (``derived``);
   * activations between layers are channels-last in the compute dtype; the last block of each returned stage also
     writes the stage's fp32 NCHW map; the stem reads the fp32 NCHW canvas; the max pool is a launch of its own;
-  * the whole network is one precomputed plan handed to ``sdetr_backbone_run`` (one ctypes call per forward);
+  * the whole network is one precomputed plan (``build_plan``, filled through ``backbone_base.PlanBuilder`` as the other
+    backbones' are) handed to ``sdetr_backbone_run`` (one ctypes call per forward);
   * ``set_dtype``: fp32 (default) multiplies at fp32 accuracy (exact three-way bf16 split of both operands); bf16 /
     fp16 take one 16-bit product with fp32 accumulation and keep the activations in that type between layers.
 The HIP path serves every ``groups == 1`` arch without dilation or DCN: resnet18/34/50/101/152 and wide_resnet50_2 /
@@ -22,8 +23,10 @@ The HIP path serves every ``groups == 1`` arch without dilation or DCN: resnet18
 plain-torch composite (``F.conv2d`` + the frozen affine), which is also the default autograd path.  A CPU tensor on the
 HIP form raises: the hot path has no CPU fallback.
 
-Training in HIP (``set_train_form("hip")``, ``csrc/backbone_backward.hip``): a forward that needs autograd runs the same
-forward plan inside one autograd node; its backward is one ``sdetr_backbone_bwd_run`` call over ``build_backward_plan``:
+Training in HIP (``set_train_form("hip")``, ``csrc/backbone_backward.hip``; the interface and its autograd node are
+``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored activations and ``_run_backward``): a forward
+that needs autograd runs the same forward plan inside one autograd node; its backward is one ``sdetr_backbone_bwd_run``
+call over ``build_backward_plan``:
 one backward-data launch per conv whose input has a trainable conv upstream, one backward-weight launch per trainable
 conv (plus the fixed-order reduction where a reduction is split), one ingest launch per returned map.  The stored
 activations are the ReLU masks and the weight-gradient operands; no activation is copied.  Served: ``hip_form()``
@@ -31,15 +34,13 @@ archs with a frozen stem (``freeze_indices`` non-empty), an input without gradie
 raises at forward.  Stem / max-pool backward and float16 training are out of scope.
 """
 import ctypes
-import os
-import weakref
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Type, Union
 
 import torch
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import HipBackbone
+from .backbone_base import HipBackbone, PlanBuilder
 from .derived import derived
 
 
@@ -197,9 +198,6 @@ class ResNet(nn.Module):
                                 dilation=self.dilation, norm_layer=norm_layer, with_dcn=with_dcn))
         return nn.Sequential(*layers)
 
-    def stages(self) -> List[nn.Sequential]:
-        return [getattr(self, f"layer{i + 1}") for i in range(self.num_stages)]
-
 
 ARCHS = {
     "resnet18": dict(block=BasicBlock, layers=(2, 2, 2, 2)),
@@ -253,7 +251,6 @@ class ResNetBackbone(HipBackbone):
         self.dilation = net.dilation
         self.num_channels = [64 * self.block.expansion * 2 ** i for i in self.return_indices]
         self.compute_dtype = torch.float32
-        self.train_form = "torch"
         if weights is not None:
             self.load_weights(weights)
         if len(freeze_indices) > 0:
@@ -261,20 +258,6 @@ class ResNetBackbone(HipBackbone):
                 self._freeze(m)
         for i in freeze_indices:
             self._freeze(getattr(self, f"layer{i + 1}"))
-
-    def load_weights(self, weights: Union[str, Dict[str, Tensor]]):
-        """A local checkpoint path or a state dict (possibly under ``"model"``); non-strict, entries whose shape does not
-        match are skipped (``util.utils.load_state_dict`` of the reference).  Never downloads."""
-        if isinstance(weights, str):
-            if not os.path.exists(weights):
-                raise FileNotFoundError(f"ResNetBackbone: no weight file at {weights} (nothing is downloaded)")
-            weights = torch.load(weights, map_location="cpu")
-        if "model" in weights and isinstance(weights["model"], dict):
-            weights = weights["model"]
-        own = self.state_dict()
-        matched = {k: v for k, v in weights.items()
-                   if k not in own or k.endswith("num_batches_tracked") or own[k].shape == v.shape}
-        return self.load_state_dict(matched, strict=False)
 
     def stages(self) -> List[nn.Sequential]:
         return [getattr(self, f"layer{i + 1}") for i in range(self.num_stages)]
@@ -302,13 +285,6 @@ class ResNetBackbone(HipBackbone):
         return all(isinstance(m, FrozenBatchNorm2d) for m in norms)
 
     # ------------------------------------------------------------------------------------------ forward
-    def forward(self, x: Tensor) -> Dict[str, Tensor]:
-        if self.train_form == "hip" and self._needs_autograd(x):
-            return self.forward_hip_train(x)
-        if self._needs_autograd(x) or not self.hip_form():
-            return self.forward_torch(x)
-        return self.forward_hip(x)
-
     def forward_torch(self, x: Tensor) -> Dict[str, Tensor]:
         """The differentiable composite (``F.conv2d`` + the frozen affine) on the input's device."""
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
@@ -338,48 +314,46 @@ class ResNetBackbone(HipBackbone):
                        extra=(float(bn.eps), precision, self.compute_dtype, layout))
 
     def build_plan(self, x: Tensor, splits: int = 0, acts: Optional[Dict[str, Tensor]] = None):
-        """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep)`` where
-        ``outputs`` are the returned fp32 NCHW maps and ``keep`` every tensor the plan points into.  ``acts`` (a dict)
-        receives the channels-last output of every op under the op's name (``"conv1"``, ``"pool"``,
-        ``"layer2.0.conv1"``, ``"layer2.0.downsample.0"`` ..), in op order: what the training backward reads."""
+        """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
+        ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op
+        (``"conv1"``, ``"pool"``, ``"layer2.0.conv1"``, ``"layer2.0.downsample.0"`` ..).  ``acts`` (a dict) receives the
+        channels-last output of every op under the op's name, in op order: what the training backward reads."""
         names = {id(m): n for n, m in self.named_modules() if isinstance(m, nn.Conv2d)}
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
-        dev, batch = x.device, x.shape[0]
-        ops: List[_hip.BackboneOpStruct] = []
-        keep: List[Tensor] = [x]
-        outputs: Dict[str, Tensor] = {}
+        batch = x.shape[0]
+        pb = PlanBuilder(_hip.BackboneOpStruct, x, batch=batch)
+        new, keep, outputs = pb.new, pb.keep, pb.outputs
 
         def conv_op(conv, bn, src, h, w, relu, residual=None, nchw_out=None, x_nchw=False):
             k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
             ho, wo = _out_hw(h, k, s, p), _out_hw(w, k, s, p)
             packed, bias = self._packed(conv, bn, 1 if x_nchw else 0)
-            out = torch.empty(batch, ho, wo, conv.out_channels, device=dev, dtype=act)
-            keep.extend((packed, bias, out))
+            keep.extend((packed, bias))
+            out = new((batch, ho, wo, conv.out_channels), act)
             if acts is not None:
                 acts[names[id(conv)]] = out
-            ops.append(_hip.BackboneOpStruct(0, src.data_ptr(), packed.data_ptr(), bias.data_ptr(), _hip.ptr(residual),
-                                             out.data_ptr(), _hip.ptr(nchw_out), batch, conv.in_channels, h, w,
-                                             conv.out_channels, k, s, p, 1 if relu else 0, 1 if x_nchw else 0, splits))
+            pb.op(names[id(conv)], 0, x=src.data_ptr(), weight=packed.data_ptr(), bias=bias.data_ptr(),
+                  residual=_hip.ptr(residual), out=out.data_ptr(), out_nchw=_hip.ptr(nchw_out), in_channels=conv.in_channels,
+                  height=h, width=w, out_channels=conv.out_channels, kernel_size=k, stride=s, padding=p,
+                  relu=1 if relu else 0, x_nchw=1 if x_nchw else 0, splits=splits)
             return out, ho, wo
 
         h, w = x.shape[2], x.shape[3]
         y, h, w = conv_op(self.conv1, self.bn1, x, h, w, True, x_nchw=True)
         ho, wo = _out_hw(h, 3, 2, 1), _out_hw(w, 3, 2, 1)
-        pooled = torch.empty(batch, ho, wo, 64, device=dev, dtype=act)
-        keep.append(pooled)
+        pooled = new((batch, ho, wo, 64), act)
         if acts is not None:
             acts["pool"] = pooled
-        ops.append(_hip.BackboneOpStruct(1, y.data_ptr(), None, None, None, pooled.data_ptr(), None, batch, 64, h, w, 64,
-                                         3, 2, 1, 0, 0, 0))
+        pb.op("pool", 1, x=y.data_ptr(), out=pooled.data_ptr(), in_channels=64, height=h, width=w, out_channels=64,
+              kernel_size=3, stride=2, padding=1)
         y, h, w = pooled, ho, wo
         for i, stage in enumerate(self.stages()):
             for j, blk in enumerate(stage):
                 last = i in self.return_indices and j == len(stage) - 1
                 nchw = None
                 if last:
-                    nchw = torch.empty(batch, self._block_out_channels(blk), _out_hw(h, 1, blk.stride, 0),
-                                       _out_hw(w, 1, blk.stride, 0), device=dev, dtype=torch.float32)
-                    keep.append(nchw)
+                    nchw = new((batch, self._block_out_channels(blk), _out_hw(h, 1, blk.stride, 0),
+                                _out_hw(w, 1, blk.stride, 0)), torch.float32)
                     outputs[f"layer{i + 1}"] = nchw
                 identity = y
                 if blk.downsample is not None:
@@ -390,13 +364,14 @@ class ResNetBackbone(HipBackbone):
                     y, h, w = conv_op(blk.conv3, blk.bn3, t, th, tw, True, residual=identity, nchw_out=nchw)
                 else:
                     y, h, w = conv_op(blk.conv2, blk.bn2, t, th, tw, True, residual=identity, nchw_out=nchw)
-        return ops, outputs, keep
+        return pb.ops, outputs, keep, pb.names
 
     @staticmethod
     def _block_out_channels(blk) -> int:
         return blk.conv3.out_channels if isinstance(blk, Bottleneck) else blk.conv2.out_channels
 
-    def forward_hip(self, x: Tensor, splits: int = 0, acts: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+    def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
+        """``state`` (a dict): a training forward; it receives ``"acts"``, see ``build_plan``."""
         if x.dtype != torch.float32:
             x = x.float()
         _hip.require_device("ResNetBackbone", x=x)
@@ -404,38 +379,23 @@ class ResNetBackbone(HipBackbone):
             _hip.require_device("ResNetBackbone", parameter=t.detach())
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"ResNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
-        ops, outputs, keep = self.build_plan(x, splits, acts)
+        acts = None if state is None else state.setdefault("acts", {})
+        ops, outputs, keep, _ = self.build_plan(x, splits, acts)
         self._run_plan(_hip.BackboneOpStruct, "sdetr_backbone", ops, x.device)
         return outputs
 
     # ------------------------------------------------------------------------------------------ training in HIP
-    def set_train_form(self, form: str):
-        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
-        (the HIP forward plan inside an autograd node whose backward is one ``sdetr_backbone_bwd_run`` call, see
-        ``forward_hip_train``).  ``"hip"`` on a module or input that is not eligible (``hip_train_reason``) raises at
-        forward: it never falls back."""
-        if form not in ("torch", "hip"):
-            raise ValueError(f"ResNetBackbone.set_train_form: {form!r} is not 'torch' / 'hip'")
-        self.train_form = form
-        return self
+    # (the interface is HipBackbone's: the node keeps the plan's channels-last activations; its backward runs
+    # ``build_backward_plan`` with one ``sdetr_backbone_bwd_run`` call and returns the fp32 weight gradients)
+    train_reasons = ("the architecture is not one the HIP kernels serve (grouped / dilated convs, a bias or a norm layer "
+                     "other than FrozenBatchNorm2d)",
+                     "the stem (conv1) is not frozen: the stem and max-pool backward are out of scope")
 
-    def hip_train_reason(self, x: Optional[Tensor] = None) -> Optional[str]:
-        """Why the ``"hip"`` training form cannot serve this module (and input ``x``); ``None`` when it can."""
-        if not self.hip_form():
-            return "the architecture is not one the HIP kernels serve (grouped / dilated convs, a bias or a norm layer " \
-                   "other than FrozenBatchNorm2d)"
-        if any(p.requires_grad for p in list(self.conv1.parameters()) + list(self.bn1.parameters())):
-            return "the stem (conv1) is not frozen: the stem and max-pool backward are out of scope"
-        if self.compute_dtype not in (torch.float32, torch.bfloat16):
-            return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
-        if x is not None and x.requires_grad:
-            return "the input requires a gradient: the gradient to the image is out of scope"
-        return None
+    def _stem_modules(self):
+        return self.conv1, self.bn1
 
-    def hip_train_form(self, x: Optional[Tensor] = None) -> bool:
-        """True when ``set_train_form("hip")`` can train this module (on input ``x``): ``hip_form()``, a frozen stem, an
-        input without gradient and a float32 / bfloat16 compute dtype."""
-        return self.hip_train_reason(x) is None
+    def _output_name(self, i: int) -> str:
+        return f"layer{i + 1}"
 
     def _blocks(self, height: int, width: int):
         """Every residual block in forward order with its convs ``(name, conv, bn, in_h, in_w)``, its input tensor's name
@@ -540,33 +500,22 @@ class ResNetBackbone(HipBackbone):
     def _trainable_convs(self) -> List[Tuple[str, nn.Conv2d]]:
         return [(n, m) for n, m in self.named_modules() if isinstance(m, nn.Conv2d) and m.weight.requires_grad]
 
-    def forward_hip_train(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
-        """The ``"hip"`` training form: the HIP forward plan as one autograd node.  The node keeps the plan's channels-last
-        activations (no copy); its backward runs ``build_backward_plan`` with one ``sdetr_backbone_bwd_run`` call and
-        returns the fp32 weight gradients to autograd, which accumulates them into ``.grad``."""
-        reason = self.hip_train_reason(x)
-        if reason is not None:
-            raise RuntimeError(f"ResNetBackbone: the 'hip' training form cannot run: {reason}")
-        named = self._trainable_convs()
-        maps = _BackboneTrainFunction.apply(self, x, splits, tuple(n for n, _ in named), *[m.weight for _, m in named])
-        return dict(zip([f"layer{i + 1}" for i in sorted(self.return_indices)], maps))
+    def _trainable(self) -> List[Tuple[str, Tensor]]:
+        return [(n, m.weight) for n, m in self._trainable_convs()]
 
     def saved_activations(self) -> List[Tuple[str, Tensor]]:
         """Test hook (read-only): ``(op name, post-activation output [B, H, W, C] in the compute dtype)`` of every op with
         a ReLU, in op order (the stem first), as stored by the last ``"hip"`` training forward.  Valid while that
         forward's autograd graph is alive."""
-        acts = self.__dict__.get("_train_acts")
-        acts = acts() if acts is not None else None
-        if acts is None:
-            raise RuntimeError("ResNetBackbone.saved_activations: no 'hip' training forward is alive")
-        return [(n, t) for n, t in acts.items() if n != "pool" and ".downsample." not in n]
+        return [(n, t) for n, t in self._train_state()["acts"].items() if n != "pool" and ".downsample." not in n]
 
-    def _run_backward(self, acts: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
+    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
                       ) -> Dict[str, Tensor]:
         """Runs the backward plan on the stored activations; returns ``{conv name: fp32 weight gradient}``."""
         batch, _, height, width = shape
         plan = self.build_backward_plan(batch, height, width)
         modules = dict(self.named_modules())
+        acts = state["acts"]
         dev = acts["pool"].device
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
         tensors: Dict[str, Tensor] = dict(acts)
@@ -594,46 +543,13 @@ class ResNetBackbone(HipBackbone):
                     tensors[d["out"]] = torch.empty((batch, d["height"], d["width"], d["in_channels"]), device=dev, dtype=act)
                 keep.extend(t for t in (weight, scale) if t is not None)
             ops.append(_hip.BackboneBwdOpStruct(
-                kinds[d["kind"]], tensors[d["dz"]].data_ptr(), _hip.ptr(tensors.get(d["x"])), _hip.ptr(weight),
-                _hip.ptr(scale), _hip.ptr(tensors.get(d["add"])), _hip.ptr(tensors.get(d["mask"])),
-                tensors[d["out"]].data_ptr(), batch, d["in_channels"], d["height"], d["width"], d["out_channels"],
-                d["kernel_size"], d["stride"], d["padding"], splits))
-        grads = {d["conv"]: tensors[d["out"]] for d in plan if d["kind"] == "wgrad"}
-        if not ops:
-            return grads
-        lib, precision = self._lib(), self._precision()
-        arr = (_hip.BackboneBwdOpStruct * len(ops))(*ops)
-        ws_bytes = lib.sdetr_backbone_bwd_workspace_bytes(arr, len(ops), precision)
-        if ws_bytes < 0:
-            _hip.check(-1, "ResNetBackbone (backward workspace)", lib)
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
-        _hip.launch("sdetr_backbone_bwd_run", lib, dev, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
-                    what="ResNetBackbone (backward run)")
-        return grads
-
-
-class _ActDict(dict):
-    """A dict that can be weakly referenced (``ResNetBackbone.saved_activations``)."""
-
-
-class _BackboneTrainFunction(torch.autograd.Function):
-    """``ResNetBackbone.forward_hip_train``: inputs are the trainable conv weights, outputs the returned fp32 maps."""
-
-    @staticmethod
-    def forward(ctx, backbone: "ResNetBackbone", x: Tensor, splits: int, names: Tuple[str, ...], *weights: Tensor):
-        acts = _ActDict()
-        outputs = backbone.forward_hip(x, splits, acts)
-        ctx.backbone, ctx.acts, ctx.names, ctx.splits = backbone, acts, names, splits
-        ctx.shape = tuple(x.shape)
-        ctx.keys = sorted(outputs)
-        backbone.__dict__["_train_acts"] = weakref.ref(acts)
-        return tuple(outputs[k] for k in ctx.keys)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        dws = ctx.backbone._run_backward(ctx.acts, ctx.shape, dict(zip(ctx.keys, grads)), ctx.splits)
-        return (None, None, None, None) + tuple(dws.get(n) for n in ctx.names)
+                kind=kinds[d["kind"]], dz=tensors[d["dz"]].data_ptr(), x=_hip.ptr(tensors.get(d["x"])), weight=_hip.ptr(weight),
+                scale=_hip.ptr(scale), add=_hip.ptr(tensors.get(d["add"])), mask=_hip.ptr(tensors.get(d["mask"])),
+                out=tensors[d["out"]].data_ptr(), batch=batch, splits=splits,
+                **{f: d[f] for f in ("in_channels", "height", "width", "out_channels", "kernel_size", "stride", "padding")}))
+        if ops:
+            self._run_plan(_hip.BackboneBwdOpStruct, "sdetr_backbone_bwd", ops, dev)
+        return {d["conv"]: tensors[d["out"]] for d in plan if d["kind"] == "wgrad"}
 
 
 def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: bool = True,

@@ -1,8 +1,11 @@
 """What the four HIP backbones (``backbone.py``, ``convnext.py``, ``focalnet.py``, ``swin.py``) share: ``HipBackbone``,
-the module base with the precision switch, the torch / HIP dispatch, checkpoint loading, the operand packers and the
-launch of a plan; ``PlanBuilder``, the op list a ``build_plan`` fills; and the two parameter-free holder modules
-``Permute`` and ``StochasticDepth``."""
+the module base with the precision switch, the torch / HIP dispatch, checkpoint loading, the operand packers, the
+launch of a plan and the training interface (``set_train_form``, ``hip_train_reason``, ``forward_hip_train`` and the one
+autograd node behind it: a backbone with a HIP backward adds its forward's stored state and ``_run_backward``);
+``PlanBuilder``, the op list a ``build_plan`` fills; and the two parameter-free holder modules ``Permute`` and
+``StochasticDepth``."""
 import os
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -50,10 +53,12 @@ class StochasticDepth(nn.Module):
 class PlanBuilder:
     """The op list of one forward: ``ops`` (structs of ``struct_type``), ``names`` (one label per op), ``keep`` (every
     tensor the ops point into) and ``outputs`` (the returned maps).  ``defaults`` are the fields every op of the plan
-    starts from (the batch, the splits ..); the struct's remaining fields start at zero / null."""
+    starts from (the batch, the splits ..); the struct's remaining fields start at zero / null.  An op's kind goes into
+    the struct's first field, whatever the header calls it (``kind``, or ``op`` in ``sdetr_backbone_op``)."""
 
     def __init__(self, struct_type, x: Tensor, **defaults):
         self.struct_type, self.device, self.defaults = struct_type, x.device, defaults
+        self.kind_field = struct_type._fields_[0][0]
         self.ops: list = []
         self.names: List[str] = []
         self.keep: List[Tensor] = [x]
@@ -65,7 +70,7 @@ class PlanBuilder:
         return t
 
     def op(self, name: str, kind: int, **fields):
-        self.ops.append(self.struct_type(kind=kind, **{**self.defaults, **fields}))
+        self.ops.append(self.struct_type(**{self.kind_field: kind, **self.defaults, **fields}))
         self.names.append(name)
 
     def layer_norm(self, name: str, kind: int, affine: Tuple[Tensor, Tensor], eps: float, src: Tensor, out: Tensor, h: int,
@@ -77,9 +82,42 @@ class PlanBuilder:
                 height=h, width=w, out_channels=c, out_f32=1 if out_f32 else 0, eps=float(eps), **fields)
 
 
+class _TrainState(dict):
+    """What one ``"hip"`` training forward stored for its backward; a dict that can be weakly referenced."""
+
+
+class _TrainFunction(torch.autograd.Function):
+    """``HipBackbone.forward_hip_train``: inputs are the trainable parameters, outputs the returned fp32 maps."""
+
+    @staticmethod
+    def forward(ctx, backbone: "HipBackbone", x: Tensor, splits: int, names: Tuple[str, ...], *params: Tensor):
+        state = _TrainState()
+        outputs = backbone.forward_hip(x, splits, state)
+        ctx.backbone, ctx.state, ctx.names, ctx.splits = backbone, state, names, splits
+        ctx.shape = tuple(x.shape)
+        ctx.keys = sorted(outputs)
+        backbone.__dict__["_train_state_ref"] = weakref.ref(state)
+        return tuple(outputs[k] for k in ctx.keys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        got = ctx.backbone._run_backward(ctx.state, ctx.shape, dict(zip(ctx.keys, grads)), ctx.splits)
+        return (None, None, None, None) + tuple(None if n not in got else got[n].contiguous() for n in ctx.names)
+
+
 class HipBackbone(nn.Module):
     """A backbone with a HIP inference form (``forward_hip``, one plan per forward) and a plain-torch composite
-    (``forward_torch``, the autograd path); a subclass gives both, ``hip_form()`` and ``compute_dtype``."""
+    (``forward_torch``, the autograd path); a subclass gives both, ``hip_form()`` and ``compute_dtype``.
+
+    One with a HIP backward also gives ``train_reasons`` and ``_stem_modules()`` (what ``hip_train_reason`` says in its
+    own words), ``_trainable()`` (``[(name, tensor)]``: the autograd node's inputs), ``_output_name(i)``,
+    ``forward_hip(x, splits, state)`` (``state``, a dict, receives what the backward reads) and
+    ``_run_backward(state, shape, cotangents, splits)`` (``{name: fp32 gradient}``)."""
+
+    train_form = "torch"
+    # of a backbone with a HIP backward: why hip_form() is False, why a trainable stem is not served
+    train_reasons: Optional[Tuple[str, str]] = None
 
     @staticmethod
     def _freeze(module: nn.Module):
@@ -119,9 +157,64 @@ class HipBackbone(nn.Module):
         return x.requires_grad or any(p.requires_grad for p in self.parameters())
 
     def forward(self, x: Tensor) -> Dict[str, Tensor]:
+        if self.train_form == "hip" and self._needs_autograd(x):
+            return self.forward_hip_train(x)
         if self._needs_autograd(x) or not self.hip_form():
             return self.forward_torch(x)
         return self.forward_hip(x)
+
+    # ------------------------------------------------------------------------------------------ training in HIP
+    def set_train_form(self, form: str):
+        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
+        (the HIP forward plan inside an autograd node whose backward is one plan too, see ``forward_hip_train``).
+        ``"hip"`` on a module or input that is not eligible (``hip_train_reason``) raises at forward: it never falls
+        back."""
+        if form not in ("torch", "hip"):
+            raise ValueError(f"{type(self).__name__}.set_train_form: {form!r} is not 'torch' / 'hip'")
+        self.train_form = form
+        return self
+
+    def _stem_modules(self) -> Sequence[nn.Module]:
+        """The modules below the first stage, whose backward is out of scope."""
+        return ()
+
+    def hip_train_reason(self, x: Optional[Tensor] = None) -> Optional[str]:
+        """Why the ``"hip"`` training form cannot serve this module (and input ``x``); ``None`` when it can."""
+        if self.train_reasons is None:
+            return "this backbone has no HIP backward"
+        if not self.hip_form():
+            return self.train_reasons[0]
+        if any(p.requires_grad for m in self._stem_modules() for p in m.parameters()):
+            return self.train_reasons[1]
+        if self.compute_dtype not in (torch.float32, torch.bfloat16):
+            return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
+        if x is not None and x.requires_grad:
+            return "the input requires a gradient: the gradient to the image is out of scope"
+        return None
+
+    def hip_train_form(self, x: Optional[Tensor] = None) -> bool:
+        """True when ``set_train_form("hip")`` can train this module (on input ``x``): ``hip_form()``, a frozen stem, an
+        input without gradient and a float32 / bfloat16 compute dtype."""
+        return self.hip_train_reason(x) is None
+
+    def forward_hip_train(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+        """The ``"hip"`` training form: the HIP forward plan as one autograd node.  The node keeps what the backward
+        reads (the plan's own activations, no copy); its backward is one ``_run_backward`` call and returns the fp32
+        parameter gradients to autograd, which accumulates them into ``.grad``."""
+        reason = self.hip_train_reason(x)
+        if reason is not None:
+            raise RuntimeError(f"{type(self).__name__}: the 'hip' training form cannot run: {reason}")
+        named = self._trainable()
+        maps = _TrainFunction.apply(self, x, splits, tuple(n for n, _ in named), *[t for _, t in named])
+        return dict(zip([self._output_name(i) for i in sorted(self.return_indices)], maps))
+
+    def _train_state(self) -> dict:
+        """What the last ``"hip"`` training forward stored; valid while that forward's autograd graph is alive."""
+        state = self.__dict__.get("_train_state_ref")
+        state = state() if state is not None else None
+        if state is None:
+            raise RuntimeError(f"{type(self).__name__}: no 'hip' training forward is alive")
+        return state
 
     def _precision(self) -> int:
         return 0 if self.compute_dtype == torch.float32 else 1

@@ -23,16 +23,16 @@ By default a call with grad enabled on something that requires grad takes the pl
 ``F.layer_norm``, ``F.linear``, ``F.gelu``, row-mode stochastic depth), which is the default autograd path.  A CPU tensor
 on the HIP form raises: the hot path has no CPU fallback.
 
-Training in HIP (``set_train_form("hip")``, ``csrc/convnext_backward.hip``): a forward that needs autograd runs the same
-plan inside one autograd node, with three additions to its launches (``aux`` / ``row_scale`` of ``sdetr_convnext_op``):
-the depthwise launch also stores its fp32 values before the LayerNorm, Linear 1 its values before the GELU, and Linear 2
-multiplies by the block's stochastic-depth factor per sample (drawn on the device exactly as ``StochasticDepth`` draws
-it).  The backward is one ``sdetr_convnext_bwd_run`` call over ``_backward_ops``: it stops below the lowest trainable
+Training in HIP (``set_train_form("hip")``, ``csrc/convnext_backward.hip``; the interface and its autograd node are
+``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored state and ``_run_backward``): a forward that
+needs autograd runs the same plan inside one autograd node, with three additions to its launches (``aux`` /
+``row_scale`` of ``sdetr_convnext_op``): the depthwise launch also stores its fp32 values before the LayerNorm, Linear 1
+its values before the GELU, and Linear 2 multiplies by the block's stochastic-depth factor per sample (drawn on the
+device exactly as ``StochasticDepth`` draws it).  The backward is one ``sdetr_convnext_bwd_run`` call over ``_backward_ops``: it stops below the lowest trainable
 module and returns fp32 gradients for the parameters that require them.  Served: ``hip_form()`` with a frozen stem, an
 input without gradient, float32 or bfloat16.  The stem's backward, a gradient to the image and float16 training are out
 of scope; anything else raises at forward.
 """
-import weakref
 from functools import partial
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -172,7 +172,6 @@ class ConvNeXtBackbone(HipBackbone):
         self.features = net.features
         self.num_channels = [self.block_setting[i].input_channels for i in self.return_indices]
         self.compute_dtype = torch.float32
-        self.train_form = "torch"
         if weights is not None:
             self.load_weights(weights)
         if len(freeze_indices) > 0:
@@ -298,7 +297,9 @@ class ConvNeXtBackbone(HipBackbone):
                 index += 1
         return pb.ops, outputs, keep, pb.names
 
-    def forward_hip(self, x: Tensor, splits: int = 0, train: Optional[dict] = None) -> Dict[str, Tensor]:
+    def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
+        """``state`` (a dict): a training forward; it receives ``"first"``, ``"acts"`` and ``"factors"``, see
+        ``build_plan``."""
         if x.dtype != torch.float32:
             x = x.float()
         _hip.require_device("ConvNeXtBackbone", x=x)
@@ -308,43 +309,24 @@ class ConvNeXtBackbone(HipBackbone):
             raise RuntimeError(f"ConvNeXtBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
         if min(x.shape[2], x.shape[3]) < 4 * 2 ** (self.num_stages - 1):
             raise RuntimeError(f"ConvNeXtBackbone: a {tuple(x.shape[2:])} canvas leaves a stage without pixels")
-        ops, outputs, keep, _ = self.build_plan(x, splits, train)
+        if state is not None:
+            state["first"] = self._first_trainable()
+        ops, outputs, keep, _ = self.build_plan(x, splits, state)
         self._run_plan(_hip.ConvnextOpStruct, "sdetr_convnext", ops, x.device)
         return outputs
 
     # ------------------------------------------------------------------------------------------ training in HIP
-    def forward(self, x: Tensor) -> Dict[str, Tensor]:
-        if self.train_form == "hip" and self._needs_autograd(x):
-            return self.forward_hip_train(x)
-        return super().forward(x)
+    # (the interface is HipBackbone's: the node keeps the activations the backward reads; its backward is one
+    # ``sdetr_convnext_bwd_run`` call over ``_backward_ops`` and returns the fp32 parameter gradients)
+    train_reasons = ("the architecture is not one the HIP kernels serve (a block other than CNBlock with nn.LayerNorm, a "
+                     "norm other than LayerNorm2d, or a width that is no multiple of 32 up to 3072)",
+                     "the stem (features.0) is not frozen: the 4x4 patchify backward is out of scope")
 
-    def set_train_form(self, form: str):
-        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
-        (the HIP forward plan inside an autograd node whose backward is one ``sdetr_convnext_bwd_run`` call, see
-        ``forward_hip_train``).  ``"hip"`` on a module or input that is not eligible (``hip_train_reason``) raises at
-        forward: it never falls back."""
-        if form not in ("torch", "hip"):
-            raise ValueError(f"ConvNeXtBackbone.set_train_form: {form!r} is not 'torch' / 'hip'")
-        self.train_form = form
-        return self
+    def _stem_modules(self):
+        return (self.features[0],)
 
-    def hip_train_reason(self, x: Optional[Tensor] = None) -> Optional[str]:
-        """Why the ``"hip"`` training form cannot serve this module (and input ``x``); ``None`` when it can."""
-        if not self.hip_form():
-            return "the architecture is not one the HIP kernels serve (a block other than CNBlock with nn.LayerNorm, a " \
-                   "norm other than LayerNorm2d, or a width that is no multiple of 32 up to 3072)"
-        if any(p.requires_grad for p in self.features[0].parameters()):
-            return "the stem (features.0) is not frozen: the 4x4 patchify backward is out of scope"
-        if self.compute_dtype not in (torch.float32, torch.bfloat16):
-            return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
-        if x is not None and x.requires_grad:
-            return "the input requires a gradient: the gradient to the image is out of scope"
-        return None
-
-    def hip_train_form(self, x: Optional[Tensor] = None) -> bool:
-        """True when ``set_train_form("hip")`` can train this module (on input ``x``): ``hip_form()``, a frozen stem, an
-        input without gradient and a float32 / bfloat16 compute dtype."""
-        return self.hip_train_reason(x) is None
+    def _output_name(self, i: int) -> str:
+        return f"features.{2 * i + 1}"
 
     def _sequence(self) -> List[Tuple[str, str, nn.Module]]:
         """``(kind, name, module)`` of every block (``"block"``) and down-sampler (``"down"``) in forward order."""
@@ -364,24 +346,6 @@ class ConvNeXtBackbone(HipBackbone):
 
     def _trainable(self) -> List[Tuple[str, nn.Parameter]]:
         return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
-
-    def forward_hip_train(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
-        """The ``"hip"`` training form: the HIP forward plan as one autograd node.  The node keeps the activations the
-        backward reads (no copy); its backward is one ``sdetr_convnext_bwd_run`` call and returns the fp32 parameter
-        gradients to autograd, which accumulates them into ``.grad``."""
-        reason = self.hip_train_reason(x)
-        if reason is not None:
-            raise RuntimeError(f"ConvNeXtBackbone: the 'hip' training form cannot run: {reason}")
-        named = self._trainable()
-        maps = _ConvNeXtTrainFunction.apply(self, x, splits, tuple(n for n, _ in named), *[p for _, p in named])
-        return dict(zip([f"features.{2 * i + 1}" for i in sorted(self.return_indices)], maps))
-
-    def _train_state(self) -> dict:
-        state = self.__dict__.get("_train_state_ref")
-        state = state() if state is not None else None
-        if state is None:
-            raise RuntimeError("ConvNeXtBackbone: no 'hip' training forward is alive")
-        return state
 
     def saved_activations(self) -> Dict[str, Tensor]:
         """Test hook (read-only): what the last ``"hip"`` training forward stored, by op name: ``<block>.in`` (the block's
@@ -450,6 +414,19 @@ class ConvNeXtBackbone(HipBackbone):
 
         def want(*params):
             return any(p is not None and p.requires_grad for p in params)
+
+        def layer_norm_bwd(name, norm, dz, x, out, c, h, w):   # out = the gradient at the LayerNorm's input rows x
+            gamma = self._f32(norm, "weight", norm.weight)
+            keep.append(gamma)
+            affine = want(norm.weight, norm.bias)
+            dgam = new((c,), torch.float32) if affine else None
+            dbet = new((c,), torch.float32) if affine else None
+            pb.op(name + " (layer norm)", 4, dz=dz.data_ptr(), x=x.data_ptr(), gamma=gamma.data_ptr(), out=out.data_ptr(),
+                  dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), channels=c, height=h, width=w, eps=float(norm.eps))
+            if want(norm.weight):
+                grads[name + ".weight"] = dgam
+            if want(norm.bias):
+                grads[name + ".bias"] = dbet
 
         # the spatial size of every module's input
         sizes, h, w = [], height // 4, width // 4
@@ -524,18 +501,7 @@ class ConvNeXtBackbone(HipBackbone):
                 pb.op(name + ".block.3 (dgrad)", 0, dz=dh.data_ptr(), weight=packed1.data_ptr(), out=dn.data_ptr(), channels=c,
                       height=h, width=w, out_channels=4 * c)
                 d = tmp("d", (batch, h, w, c), torch.float32)
-                gamma = self._f32(norm, "weight", norm.weight)
-                keep.append(gamma)
-                affine = want(norm.weight, norm.bias)
-                dgam = new((c,), torch.float32) if affine else None
-                dbet = new((c,), torch.float32) if affine else None
-                pb.op(name + ".block.2 (layer norm)", 4, dz=dn.data_ptr(), x=acts[name + ".block.0"].data_ptr(),
-                      gamma=gamma.data_ptr(), out=d.data_ptr(), dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), channels=c, height=h,
-                      width=w, eps=float(norm.eps))
-                if want(norm.weight):
-                    grads[name + ".block.2.weight"] = dgam
-                if want(norm.bias):
-                    grads[name + ".block.2.bias"] = dbet
+                layer_norm_bwd(name + ".block.2", norm, dn, acts[name + ".block.0"], d, c, h, w)
                 if want(dw.weight, dw.bias):
                     dtaps = new((49, c), torch.float32)
                     dbd = new((c,), torch.float32) if want(dw.bias) else None
@@ -580,57 +546,18 @@ class ConvNeXtBackbone(HipBackbone):
                           channels=4 * c, height=ho, width=wo, out_channels=co)
                     dn = tmp("dn", (batch, h, w, c), act)
                     pb.op(name + ".1 (pixels)", 9, dz=dpatch.data_ptr(), out=dn.data_ptr(), channels=c, height=h, width=w)
-                    gamma = self._f32(norm, "weight", norm.weight)
-                    keep.append(gamma)
-                    affine = want(norm.weight, norm.bias)
-                    dgam = new((c,), torch.float32) if affine else None
-                    dbet = new((c,), torch.float32) if affine else None
                     dy_next = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
                     flip ^= 1
-                    pb.op(name + ".0 (layer norm)", 4, dz=dn.data_ptr(), x=acts[name + ".in"].data_ptr(), gamma=gamma.data_ptr(),
-                          out=dy_next.data_ptr(), dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), channels=c, height=h, width=w,
-                          eps=float(norm.eps))
-                    if want(norm.weight):
-                        grads[name + ".0.weight"] = dgam
-                    if want(norm.bias):
-                        grads[name + ".0.bias"] = dbet
+                    layer_norm_bwd(name + ".0", norm, dn, acts[name + ".in"], dy_next, c, h, w)
                 dy = dy_next
         return pb.ops, pb.names, grads, keep
 
-    def _run_backward(self, acts: Dict[str, Tensor], factors: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]],
-                      splits: int = 0) -> Dict[str, Tensor]:
+    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
+                      ) -> Dict[str, Tensor]:
         """Runs the backward plan on the stored activations; returns ``{parameter name: fp32 gradient}``."""
-        ops, _, grads, keep = self._backward_ops(acts, factors, shape, cotangents, splits)
+        acts = state["acts"]
+        ops, _, grads, keep = self._backward_ops(acts, state["factors"], shape, cotangents, splits)
         if ops:
             dev = next(iter(acts.values())).device
             self._run_plan(_hip.ConvnextBwdOpStruct, "sdetr_convnext_bwd", ops, dev)
         return grads
-
-
-class _TrainState(dict):
-    """A dict that can be weakly referenced (``ConvNeXtBackbone.saved_activations``)."""
-
-
-class _ConvNeXtTrainFunction(torch.autograd.Function):
-    """``ConvNeXtBackbone.forward_hip_train``: inputs are the trainable parameters, outputs the returned fp32 maps."""
-
-    @staticmethod
-    def forward(ctx, backbone: "ConvNeXtBackbone", x: Tensor, splits: int, names: Tuple[str, ...], *params: Tensor):
-        state = _TrainState(first=backbone._first_trainable())
-        outputs = backbone.forward_hip(x, splits, state)
-        ctx.backbone, ctx.state, ctx.names, ctx.splits = backbone, state, names, splits
-        ctx.shape = tuple(x.shape)
-        ctx.keys = sorted(outputs)
-        backbone.__dict__["_train_state_ref"] = weakref.ref(state)
-        return tuple(outputs[k] for k in ctx.keys)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        state = ctx.state
-        dws = ctx.backbone._run_backward(state["acts"], state["factors"], ctx.shape, dict(zip(ctx.keys, grads)), ctx.splits)
-        out = []
-        for n in ctx.names:
-            g = dws.get(n)
-            out.append(None if g is None else g.contiguous())
-        return (None, None, None, None) + tuple(out)

@@ -25,6 +25,7 @@
 #include "backbone_conv_core.h"
 #include "common.h"
 #include "image_norm.h"
+#include "plan.h"
 
 namespace sdetr {
 namespace {
@@ -142,8 +143,9 @@ __global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
 // ------------------------------------------------------------------------------------------------------------ host
 
 // validated kernel arguments of one conv op (precision 0 fp32, 1 the library's 16-bit type)
-int make_conv(const char *what, const sdetr_backbone_op &o, int precision, BConv &c)
+int make_conv(const sdetr_backbone_op &o, int precision, BConv &c)
 {
+    const char *what = "sdetr_backbone (conv)";
     if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
     if (!o.x || !o.weight || !o.bias || !o.out) return fail("%s: null tensor", what);
     if (o.batch < 1 || o.in_channels < 1 || o.out_channels < 1 || o.height < 1 || o.width < 1)
@@ -169,9 +171,9 @@ int make_conv(const char *what, const sdetr_backbone_op &o, int precision, BConv
 int run_conv(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws, int64_t ws_bytes)
 {
     BConv c;
-    if (int rc = make_conv("sdetr_backbone_conv", o, precision, c)) return rc;
+    if (int rc = make_conv(o, precision, c)) return rc;
     if (conv_workspace(c) > ws_bytes || (conv_workspace(c) && !ws))
-        return fail("sdetr_backbone_conv: workspace of %lld bytes is too small (%lld needed)", (long long)ws_bytes,
+        return fail("sdetr_backbone (conv): workspace of %lld bytes is too small (%lld needed)", (long long)ws_bytes,
                     (long long)conv_workspace(c));
     c.partial = reinterpret_cast<float *>(ws);
     const bool x3 = precision == 0;
@@ -179,28 +181,61 @@ int run_conv(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws,
     else if (x3) launch_conv<true, false, 0>(s, c);
     else if (o.x_nchw) launch_conv<false, true, 0>(s, c);
     else launch_conv<false, false, 0>(s, c);
-    return check_launch("sdetr_backbone_conv");
+    return check_launch("sdetr_backbone (conv)");
 }
 
-int run_maxpool(hipStream_t s, const void *x, int batch, int h, int w, int c, int precision, void *out)
+// a max-pool op: x [batch, height, width, in_channels] -> out, both channels-last in the compute dtype
+int check_maxpool(const sdetr_backbone_op &o, int precision)
 {
-    if (precision != 0 && precision != 1) return fail("sdetr_backbone_maxpool: precision must be 0 or 1");
-    if (!x || !out) return fail("sdetr_backbone_maxpool: null tensor");
-    if (batch < 1 || h < 1 || w < 1 || c < 1 || c % 8)
-        return fail("sdetr_backbone_maxpool: bad shape (batch %d, %d x %d, channels %d: a multiple of 8)", batch, h, w, c);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15)
-        return fail("sdetr_backbone_maxpool: tensors must be 16-byte aligned");
+    const char *what = "sdetr_backbone (max pool)";
+    if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
+    if (!o.x || !o.out) return fail("%s: null tensor", what);
+    if (o.batch < 1 || o.height < 1 || o.width < 1 || o.in_channels < 1 || o.in_channels % 8)
+        return fail("%s: bad shape (batch %d, %d x %d, channels %d: a multiple of 8)", what, o.batch, o.height, o.width,
+                    o.in_channels);
+    if ((reinterpret_cast<uintptr_t>(o.x) | reinterpret_cast<uintptr_t>(o.out)) & 15)
+        return fail("%s: tensors must be 16-byte aligned", what);
+    return 0;
+}
+
+int run_maxpool(hipStream_t s, const sdetr_backbone_op &o, int precision)
+{
+    if (int rc = check_maxpool(o, precision)) return rc;
+    const int batch = o.batch, h = o.height, w = o.width, c = o.in_channels;
     const int ho = out_hw(h, 3, 2, 1), wo = out_hw(w, 3, 2, 1);
     const int64_t total = (int64_t)batch * ho * wo * (c / (precision == 0 ? 4 : 8));
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
     if (precision == 0)
-        hipLaunchKernelGGL(backbone_maxpool_kernel<true>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const char *>(x),
-                           batch, h, w, c, ho, wo, reinterpret_cast<char *>(out));
+        hipLaunchKernelGGL(backbone_maxpool_kernel<true>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const char *>(o.x),
+                           batch, h, w, c, ho, wo, reinterpret_cast<char *>(o.out));
     else
-        hipLaunchKernelGGL(backbone_maxpool_kernel<false>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const char *>(x),
-                           batch, h, w, c, ho, wo, reinterpret_cast<char *>(out));
-    return check_launch("sdetr_backbone_maxpool");
+        hipLaunchKernelGGL(backbone_maxpool_kernel<false>, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const char *>(o.x),
+                           batch, h, w, c, ho, wo, reinterpret_cast<char *>(o.out));
+    return check_launch("sdetr_backbone (max pool)");
 }
+
+// validation of one op without a launch; `need` receives its workspace bytes
+int check_op(const sdetr_backbone_op &o, int precision, int64_t &need)
+{
+    need = 0;
+    if (o.op == 0) {
+        BConv c;
+        if (int rc = make_conv(o, precision, c)) return rc;
+        need = conv_workspace(c);
+        return 0;
+    }
+    if (o.op == 1) return check_maxpool(o, precision);
+    return fail("sdetr_backbone: unknown op kind %d", o.op);
+}
+
+int run_op(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws, int64_t ws_bytes)
+{
+    if (o.op == 0) return run_conv(s, o, precision, ws, ws_bytes);
+    if (o.op == 1) return run_maxpool(s, o, precision);
+    return fail("sdetr_backbone: unknown op kind %d", o.op);
+}
+
+using BackbonePlan = Plan<sdetr_backbone_op, check_op, run_op>;
 
 }  // namespace
 }  // namespace sdetr
@@ -235,59 +270,40 @@ extern "C" int sdetr_backbone_conv_splits(const sdetr_backbone_op *op, int preci
 {
     BConv c;
     if (!op || op->op != 0) return fail("sdetr_backbone_conv_splits: not a conv op");
-    if (make_conv("sdetr_backbone_conv_splits", *op, precision, c)) return SDETR_EINVAL;
+    if (make_conv(*op, precision, c)) return SDETR_EINVAL;
     return c.splits;
 }
 
 extern "C" int64_t sdetr_backbone_workspace_bytes(const sdetr_backbone_op *ops, int n_ops, int precision)
 {
-    if (!ops || n_ops < 1) return -1;
-    int64_t need = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        if (ops[i].op != 0) continue;
-        BConv c;
-        if (make_conv("sdetr_backbone_workspace_bytes", ops[i], precision, c)) return -1;
-        need = std::max(need, conv_workspace(c));
-    }
-    return need;
+    return BackbonePlan::workspace_bytes(ops, n_ops, precision);
 }
 
 extern "C" int sdetr_backbone_conv(sdetr_stream_t stream, const sdetr_backbone_op *op, int precision, void *workspace,
                                    int64_t workspace_bytes)
 {
     if (!op || op->op != 0) return fail("sdetr_backbone_conv: not a conv op");
-    return run_conv((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
+    return run_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_backbone_maxpool(sdetr_stream_t stream, const void *x, int batch, int height, int width, int channels,
                                       int precision, void *out)
 {
-    return run_maxpool((hipStream_t)stream, x, batch, height, width, channels, precision, out);
+    sdetr_backbone_op o = {};
+    o.op = 1;
+    o.x = x;
+    o.out = out;
+    o.batch = batch;
+    o.height = height;
+    o.width = width;
+    o.in_channels = o.out_channels = channels;
+    return run_op((hipStream_t)stream, o, precision, nullptr, 0);
 }
 
 extern "C" int sdetr_backbone_run(sdetr_stream_t stream, const sdetr_backbone_op *ops, int n_ops, int precision,
                                   void *workspace, int64_t workspace_bytes)
 {
-    if (!ops || n_ops < 1) return fail("sdetr_backbone_run: empty plan");
-    // validate the whole plan before the first launch
-    for (int i = 0; i < n_ops; ++i) {
-        BConv c;
-        if (ops[i].op == 0) {
-            if (make_conv("sdetr_backbone_run", ops[i], precision, c)) return SDETR_EINVAL;
-            if (conv_workspace(c) > workspace_bytes || (conv_workspace(c) && !workspace))
-                return fail("sdetr_backbone_run: op %d needs %lld workspace bytes", i, (long long)conv_workspace(c));
-        } else if (ops[i].op != 1) {
-            return fail("sdetr_backbone_run: op %d has unknown kind %d", i, ops[i].op);
-        }
-    }
-    for (int i = 0; i < n_ops; ++i) {
-        const sdetr_backbone_op &o = ops[i];
-        const int rc = o.op == 0 ? run_conv((hipStream_t)stream, o, precision, workspace, workspace_bytes)
-                                 : run_maxpool((hipStream_t)stream, o.x, o.batch, o.height, o.width, o.in_channels,
-                                               precision, o.out);
-        if (rc) return rc;
-    }
-    return 0;
+    return BackbonePlan::run("sdetr_backbone", stream, ops, n_ops, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_backbone_batch_images_ex(sdetr_stream_t stream, const void *const *images, const int *image_hw,

@@ -26,6 +26,7 @@
 
 #include "backbone_core.h"
 #include "common.h"
+#include "plan.h"
 
 namespace sdetr {
 namespace {
@@ -557,7 +558,8 @@ int b_out_hw(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
 int b_round32(int v) { return (v + 31) / 32 * 32; }
 
 // the checks every kind shares; fills the output size
-int check_op(const char *what, const sdetr_backbone_bwd_op &o, int precision, int &ho, int &wo)
+// precision and the conv geometry of a dgrad / wgrad op; ho x wo is the size of dz
+int check_geometry(const char *what, const sdetr_backbone_bwd_op &o, int precision, int &ho, int &wo)
 {
     if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
     if (o.batch < 1 || o.in_channels < 1 || o.out_channels < 1 || o.height < 1 || o.width < 1)
@@ -584,10 +586,11 @@ int dgrad_splits(int M, int ci, int steps, int stride, int requested)
     return std::max(1, std::min({8, 256 / tiles, steps / 4}));
 }
 
-int make_dgrad(const char *what, const sdetr_backbone_bwd_op &o, int precision, BDgrad &c)
+int make_dgrad(const sdetr_backbone_bwd_op &o, int precision, BDgrad &c)
 {
+    const char *what = "sdetr_backbone_bwd (dgrad)";
     int ho, wo;
-    if (int rc = check_op(what, o, precision, ho, wo)) return rc;
+    if (int rc = check_geometry(what, o, precision, ho, wo)) return rc;
     if (!o.dz || !o.weight || !o.out) return fail("%s: null tensor", what);
     if ((reinterpret_cast<uintptr_t>(o.dz) | reinterpret_cast<uintptr_t>(o.weight)) & 15)
         return fail("%s: dz and weight must be 16-byte aligned", what);
@@ -635,10 +638,11 @@ int wgrad_splits(int co, int ci, int kk2, int steps, int requested)
     return std::max(1, std::min({128, (512 + tiles - 1) / tiles, steps / 4}));
 }
 
-int make_wgrad(const char *what, const sdetr_backbone_bwd_op &o, int precision, BWgrad &c)
+int make_wgrad(const sdetr_backbone_bwd_op &o, int precision, BWgrad &c)
 {
+    const char *what = "sdetr_backbone_bwd (wgrad)";
     int ho, wo;
-    if (int rc = check_op(what, o, precision, ho, wo)) return rc;
+    if (int rc = check_geometry(what, o, precision, ho, wo)) return rc;
     if (!o.dz || !o.x || !o.scale || !o.out) return fail("%s: null tensor", what);
     if ((reinterpret_cast<uintptr_t>(o.dz) | reinterpret_cast<uintptr_t>(o.x)) & 15)
         return fail("%s: dz and x must be 16-byte aligned", what);
@@ -677,8 +681,9 @@ int64_t wgrad_workspace(const BWgrad &c)
     return c.splits > 1 ? (int64_t)c.splits * c.co * c.ks * c.ks * c.ci * 4 : 0;
 }
 
-int check_ingest(const char *what, const sdetr_backbone_bwd_op &o, int precision)
+int check_ingest(const sdetr_backbone_bwd_op &o, int precision)
 {
+    const char *what = "sdetr_backbone_bwd (ingest)";
     if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
     if (!o.dz || !o.out) return fail("%s: null tensor", what);
     if (o.batch < 1 || o.batch > 65535 || o.in_channels < 1 || o.height < 1 || o.width < 1 ||
@@ -687,20 +692,24 @@ int check_ingest(const char *what, const sdetr_backbone_bwd_op &o, int precision
     return 0;
 }
 
-// how much workspace an op needs (-1: invalid, the error text is set)
-int64_t op_workspace(const char *what, const sdetr_backbone_bwd_op &o, int precision)
+// validation of one op without a launch; `need` receives its workspace bytes
+int check_bwd_op(const sdetr_backbone_bwd_op &o, int precision, int64_t &need)
 {
+    need = 0;
     if (o.kind == 0) {
         BDgrad c;
-        return make_dgrad(what, o, precision, c) ? -1 : dgrad_workspace(c);
+        if (int rc = make_dgrad(o, precision, c)) return rc;
+        need = dgrad_workspace(c);
+        return 0;
     }
     if (o.kind == 1) {
         BWgrad c;
-        return make_wgrad(what, o, precision, c) ? -1 : wgrad_workspace(c);
+        if (int rc = make_wgrad(o, precision, c)) return rc;
+        need = wgrad_workspace(c);
+        return 0;
     }
-    if (o.kind == 2) return check_ingest(what, o, precision) ? -1 : 0;
-    fail("%s: unknown kind %d", what, o.kind);
-    return -1;
+    if (o.kind == 2) return check_ingest(o, precision);
+    return fail("sdetr_backbone_bwd: unknown op kind %d", o.kind);
 }
 
 template <bool X3>
@@ -731,21 +740,22 @@ void launch_wgrad(hipStream_t s, const BWgrad &c)
     }
 }
 
-int run_bwd_op(hipStream_t s, const char *what, const sdetr_backbone_bwd_op &o, int precision, void *ws, int64_t ws_bytes)
+int run_bwd_op(hipStream_t s, const sdetr_backbone_bwd_op &o, int precision, void *ws, int64_t ws_bytes)
 {
-    const int64_t need = op_workspace(what, o, precision);
-    if (need < 0) return SDETR_EINVAL;
+    int64_t need;
+    if (int rc = check_bwd_op(o, precision, need)) return rc;
     if (need > ws_bytes || (need && !ws))
-        return fail("%s: workspace of %lld bytes is too small (%lld needed)", what, (long long)ws_bytes, (long long)need);
+        return fail("sdetr_backbone_bwd: workspace of %lld bytes is too small (%lld needed)", (long long)ws_bytes,
+                    (long long)need);
     if (o.kind == 0) {
         BDgrad c;
-        make_dgrad(what, o, precision, c);
+        make_dgrad(o, precision, c);
         c.partial = reinterpret_cast<float *>(ws);
         if (precision == 0) launch_dgrad<true>(s, c);
         else launch_dgrad<false>(s, c);
     } else if (o.kind == 1) {
         BWgrad c;
-        make_wgrad(what, o, precision, c);
+        make_wgrad(o, precision, c);
         c.partial = reinterpret_cast<float *>(ws);
         if (precision == 0) launch_wgrad<true>(s, c);
         else launch_wgrad<false>(s, c);
@@ -761,8 +771,10 @@ int run_bwd_op(hipStream_t s, const char *what, const sdetr_backbone_bwd_op &o, 
                                reinterpret_cast<const char *>(o.add), reinterpret_cast<const char *>(o.mask), o.in_channels,
                                HW, reinterpret_cast<char *>(o.out));
     }
-    return check_launch(what);
+    return check_launch("sdetr_backbone_bwd");
 }
+
+using BackboneBwdPlan = Plan<sdetr_backbone_bwd_op, check_bwd_op, run_bwd_op>;
 
 }  // namespace
 }  // namespace sdetr
@@ -797,54 +809,36 @@ extern "C" int sdetr_backbone_bwd_splits(const sdetr_backbone_bwd_op *op, int pr
     if (!op) return fail("sdetr_backbone_bwd_splits: null op");
     if (op->kind == 0) {
         BDgrad c;
-        return make_dgrad("sdetr_backbone_bwd_splits", *op, precision, c) ? SDETR_EINVAL : c.splits;
+        return make_dgrad(*op, precision, c) ? SDETR_EINVAL : c.splits;
     }
     if (op->kind == 1) {
         BWgrad c;
-        return make_wgrad("sdetr_backbone_bwd_splits", *op, precision, c) ? SDETR_EINVAL : c.splits;
+        return make_wgrad(*op, precision, c) ? SDETR_EINVAL : c.splits;
     }
     return fail("sdetr_backbone_bwd_splits: not a dgrad or wgrad op");
 }
 
 extern "C" int64_t sdetr_backbone_bwd_workspace_bytes(const sdetr_backbone_bwd_op *ops, int n_ops, int precision)
 {
-    if (!ops || n_ops < 1) return -1;
-    int64_t need = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        const int64_t b = op_workspace("sdetr_backbone_bwd_workspace_bytes", ops[i], precision);
-        if (b < 0) return -1;
-        need = std::max(need, b);
-    }
-    return need;
+    return BackboneBwdPlan::workspace_bytes(ops, n_ops, precision);
 }
 
 extern "C" int sdetr_backbone_dgrad(sdetr_stream_t stream, const sdetr_backbone_bwd_op *op, int precision, void *workspace,
                                     int64_t workspace_bytes)
 {
     if (!op || op->kind != 0) return fail("sdetr_backbone_dgrad: not a dgrad op");
-    return run_bwd_op((hipStream_t)stream, "sdetr_backbone_dgrad", *op, precision, workspace, workspace_bytes);
+    return run_bwd_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_backbone_wgrad(sdetr_stream_t stream, const sdetr_backbone_bwd_op *op, int precision, void *workspace,
                                     int64_t workspace_bytes)
 {
     if (!op || op->kind != 1) return fail("sdetr_backbone_wgrad: not a wgrad op");
-    return run_bwd_op((hipStream_t)stream, "sdetr_backbone_wgrad", *op, precision, workspace, workspace_bytes);
+    return run_bwd_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
 }
 
 extern "C" int sdetr_backbone_bwd_run(sdetr_stream_t stream, const sdetr_backbone_bwd_op *ops, int n_ops, int precision,
                                       void *workspace, int64_t workspace_bytes)
 {
-    if (!ops || n_ops < 1) return fail("sdetr_backbone_bwd_run: empty plan");
-    // validate the whole plan before the first launch
-    for (int i = 0; i < n_ops; ++i) {
-        const int64_t need = op_workspace("sdetr_backbone_bwd_run", ops[i], precision);
-        if (need < 0) return SDETR_EINVAL;
-        if (need > workspace_bytes || (need && !workspace))
-            return fail("sdetr_backbone_bwd_run: op %d needs %lld workspace bytes", i, (long long)need);
-    }
-    for (int i = 0; i < n_ops; ++i)
-        if (int rc = run_bwd_op((hipStream_t)stream, "sdetr_backbone_bwd_run", ops[i], precision, workspace, workspace_bytes))
-            return rc;
-    return 0;
+    return BackboneBwdPlan::run("sdetr_backbone_bwd", stream, ops, n_ops, precision, workspace, workspace_bytes);
 }

@@ -3,8 +3,8 @@
 // ResNet (backbone.hip: folded-BN convs, EPI 0), the ConvNeXt (convnext.hip: the two Linears as 1x1 convs and the patchify
 // convs, EPI 1 / 2), the FocalNet (focalnet.hip: its Linears, the overlapped patch embedding, and h with the modulation
 // product, EPI 3 / 4) and the Swin (swin.hip: its Linears and the stem, EPI 1 / 2 / 5).  What the three row-stream families
-// share beyond it (row LayerNorm, host checks, plan entry points): backbone_rows_core.h.  Tiles and the MFMA half step:
-// backbone_core.h.
+// share beyond it (row LayerNorm, host checks): backbone_rows_core.h.  The plan entry points of every family: plan.h.
+// Tiles and the MFMA half step: backbone_core.h.
 #pragma once
 
 #include <algorithm>

@@ -1,9 +1,10 @@
 // What the row-stream backbones (convnext.hip, focalnet.hip, swin.hip) share on top of backbone_conv_core.h: the LayerNorm
 // over the channels of fp32 rows (one wave per row, the row in registers), the host checks of a rows op, the dispatch of
-// the implicit-GEMM kernel over precision and input layout, and the bodies of a family's three plan entry points.
+// the implicit-GEMM kernel over precision and input layout; with plan.h, the bodies of a family's three plan entry points.
 #pragma once
 
 #include "backbone_conv_core.h"
+#include "plan.h"
 
 namespace sdetr {
 namespace {
@@ -146,43 +147,6 @@ void launch_gemm(hipStream_t s, const BConv &c, bool x3, bool nchw)
     else if (x3) launch_conv<true, true, EPI>(s, c);
     else launch_conv<false, true, EPI>(s, c);
 }
-
-// The three plan entry points of a family `name` ("sdetr_convnext", ..) over its op struct, its validation of one op without
-// a launch (`need` receives the op's workspace bytes) and its launch of one op.
-template <class Op, int (*CheckOp)(const Op &, int, int64_t &), int (*RunOp)(hipStream_t, const Op &, int, void *, int64_t)>
-struct Plan {
-    static int64_t workspace_bytes(const Op *ops, int n_ops, int precision)
-    {
-        if (!ops || n_ops < 1) return -1;
-        int64_t most = 0;
-        for (int i = 0; i < n_ops; ++i) {
-            int64_t need;
-            if (CheckOp(ops[i], precision, need)) return -1;
-            most = std::max(most, need);
-        }
-        return most;
-    }
-
-    static int op_run(const char *name, sdetr_stream_t stream, const Op *op, int precision, void *ws, int64_t ws_bytes)
-    {
-        if (!op) return fail("%s_op_run: null op", name);
-        return RunOp((hipStream_t)stream, *op, precision, ws, ws_bytes);
-    }
-
-    static int run(const char *name, sdetr_stream_t stream, const Op *ops, int n_ops, int precision, void *ws, int64_t ws_bytes)
-    {
-        if (!ops || n_ops < 1) return fail("%s_run: empty plan", name);
-        for (int i = 0; i < n_ops; ++i) {   // validate the whole plan before the first launch
-            int64_t need;
-            if (CheckOp(ops[i], precision, need)) return SDETR_EINVAL;
-            if (need > ws_bytes || (need && !ws))
-                return fail("%s_run: op %d needs %lld workspace bytes (workspace too small)", name, i, (long long)need);
-        }
-        for (int i = 0; i < n_ops; ++i)
-            if (int rc = RunOp((hipStream_t)stream, ops[i], precision, ws, ws_bytes)) return rc;
-        return 0;
-    }
-};
 
 }  // namespace
 }  // namespace sdetr
