@@ -1620,6 +1620,12 @@ int sdetr_focalnet_run(sdetr_stream_t stream, const sdetr_focalnet_op *ops, int 
  * pointer, C % 32 != 0, a head dimension other than 32, a window other than 7 / 12, a precision outside {0, 1}, a
  * misaligned pointer or a workspace below sdetr_swin_workspace_bytes -- the largest need of the plan -- is SDETR_EINVAL
  * with a message in sdetr_last_error).  Tensors 16-byte aligned.
+ *
+ * What a training forward adds (the two last fields, as in sdetr_convnext_op; NULL = the eval launch, bit for bit):
+ *   aux        kind 1: [batch, Ho, Wo, out_channels] in the compute dtype, the values acc + bias BEFORE the GELU.  Every
+ *              element written.  Other kinds: must be NULL.
+ *   row_scale  kind 0: f32 [batch], out = (acc + bias) * row_scale[n] (+ residual): the stochastic-depth factor of the
+ *              branch the Linear closes.  Other kinds: must be NULL.
  * --------------------------------------------------------------------------------------------- */
 typedef struct sdetr_swin_op {
     int kind;
@@ -1646,6 +1652,8 @@ typedef struct sdetr_swin_op {
     int heads;
     int splits;
     float eps;
+    void *aux;
+    const float *row_scale;
 } sdetr_swin_op;
 
 int64_t sdetr_swin_workspace_bytes(const sdetr_swin_op *ops, int n_ops, int precision);
@@ -1653,6 +1661,84 @@ int sdetr_swin_op_run(sdetr_stream_t stream, const sdetr_swin_op *op, int precis
                       int64_t workspace_bytes);
 int sdetr_swin_run(sdetr_stream_t stream, const sdetr_swin_op *ops, int n_ops, int precision, void *workspace,
                    int64_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * Swin backward (training the Swin backbone, csrc/swin_backward.hip): the gradients of the ops above for a block
+ *   u = x + s1[n] * proj(attention(qkv(LN1(x)))),  y = u + s2[n] * fc2(gelu(fc1(LN2(u))))
+ * and a patch merging reduction(LN(gather(y))).  As in the ConvNeXt backward the residual-stream gradient is
+ * channels-last f32 in BOTH precisions, the GEMM operands, the qkv rows and their gradient take the compute dtype,
+ * parameter gradients are f32.  No atomics anywhere: every sum goes through fixed-order partials in the workspace, so two
+ * runs are bit-identical.  Every launch writes every element of its outputs; nothing syncs with the host.
+ *
+ * sdetr_swin_bwd_op, by kind (C = channels, K = out_channels, rows = batch * height * width):
+ *   0 dgrad, 1 wgrad, 2 rows, 3 gelu, 4 layer norm: kinds 0 .. 4 of sdetr_convnext_bwd_op with the same fields (they run
+ *               its kernels through sdetr_convnext_bwd_op_run).
+ *   5 ingest:   kind 10 of sdetr_convnext_bwd_op: dz = the f32 NCHW cotangent of a returned map, out f32 [rows, C] = dz
+ *               (+ add).
+ *   6 window attention backward.  x = the forward's qkv rows [rows][3 C] (compute dtype), bias f32 [3 C] = the qkv bias,
+ *               table f32 [heads][N][N] the expanded relative position bias, dz = the gradient at the attention rows
+ *               [rows][C] (compute dtype); window, shift, heads and the geometry as in kind 4 of sdetr_swin_op
+ *               (C = 32 * heads).  Per (window, head) the scores and the two-pass softmax P are recomputed in f32,
+ *               dP = dO V^T, dS = P (.) (dP - rowsum(P (.) dP)), dQ = 32^-0.5 dS K, dK = 32^-0.5 dS^T Q, dV = P^T dO;
+ *               the products by v_mfma_f32_16x16x32 on 16-bit operands (precision 1) or v_mfma_f32_16x16x4_f32
+ *               (precision 0).  out = the gradient at the qkv rows [rows][3 C] in the compute dtype, every element
+ *               written.  A token of the zero padding has q = k = v = bias: its dK and dV are gradient of the qkv bias
+ *               and its dQ is zero (its output row is dropped); dbias f32 [3 C] (required) = the sums of those
+ *               padded-token gradients alone (zeros in the q third, and everywhere on a map without padding).  dtable
+ *               (or NULL) f32 [(2 window - 1)^2][heads] = the gradient of relative_position_bias_table: dS summed over
+ *               batch and windows, then over the (query, key) pairs of one table entry; the pairs come as a CSR list,
+ *               order int32 [N * N] (pair indices q * N + k sorted by table entry) and offsets int32
+ *               [(2 window - 1)^2 + 1], both required with dtable (an entry outside [0, N * N) is skipped).  The -100
+ *               mask is a constant and receives nothing.  A workgroup owns one head and a strip of windows and keeps its
+ *               dS and padded sums in registers over the strip: one partial per (strip, head).
+ *   7 column sums: dz [rows][C] in the compute dtype; dbias f32 [C] = the column sums (+ add, f32 [C], or NULL): the qkv
+ *               bias gradient from kind 6's out and dbias.
+ *   8 patch-merging backward: dz = the gradient at the gathered LayerNorm rows [batch, ceil(height / 2),
+ *               ceil(width / 2), 4 C] (compute dtype), x = the f32 stream [batch, height, width, C] the merging read, gamma
+ *               f32 [4 C], eps; the statistics are recomputed from the 2 x 2 gather (the zeros beyond an odd height / width
+ *               inside them).  out f32 [batch, height, width, C] = the input gradient (+ add, f32, shaped as out, or
+ *               NULL), every pixel written exactly once, contributions to the padding dropped; dgamma / dbeta (both, or
+ *               both NULL) f32 [4 C].  4 C a multiple of 32 up to 3072.
+ * splits: 0 = automatic, n > 0 = n pieces (clamped): as in sdetr_convnext_bwd_op for kinds 0 .. 4 and 8's LayerNorm, the
+ * window strips of kind 6, the row strips of kind 7.  sdetr_swin_bwd_workspace_bytes: the largest need of a plan (-1: a
+ * bad op).  sdetr_swin_bwd_op_run runs one op; sdetr_swin_bwd_run a whole plan in order, validated before the first
+ * launch (a null pointer, a window other than 7 / 12, C != 32 * heads, a misaligned pointer or a workspace too small is
+ * SDETR_EINVAL with a message in sdetr_last_error).  Tensors 16-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct sdetr_swin_bwd_op {
+    int kind;
+    const void *dz;
+    const void *x;
+    const void *weight;
+    const float *scale;
+    const float *gamma;
+    const float *add;
+    const float *bias;
+    const float *table;
+    const int *order;
+    const int *offsets;
+    void *out;
+    float *dbias;
+    float *dgamma;
+    float *dbeta;
+    float *dtable;
+    int batch;
+    int channels;
+    int height;
+    int width;
+    int out_channels;
+    int window;
+    int shift;
+    int heads;
+    int splits;
+    float eps;
+} sdetr_swin_bwd_op;
+
+int64_t sdetr_swin_bwd_workspace_bytes(const sdetr_swin_bwd_op *ops, int n_ops, int precision);
+int sdetr_swin_bwd_op_run(sdetr_stream_t stream, const sdetr_swin_bwd_op *op, int precision, void *workspace,
+                          int64_t workspace_bytes);
+int sdetr_swin_bwd_run(sdetr_stream_t stream, const sdetr_swin_bwd_op *ops, int n_ops, int precision, void *workspace,
+                       int64_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * Contrastive denoising queries (models/bricks/denoising.py:GenerateCDNQueries), csrc/denoising.hip.

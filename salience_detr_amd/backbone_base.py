@@ -178,6 +178,10 @@ class HipBackbone(nn.Module):
         """The modules below the first stage, whose backward is out of scope."""
         return ()
 
+    def _extra_train_reason(self) -> Optional[str]:
+        """A backbone's own eligibility rule on top of the shared ones (``hip_train_reason`` asks it); ``None``: eligible."""
+        return None
+
     def hip_train_reason(self, x: Optional[Tensor] = None) -> Optional[str]:
         """Why the ``"hip"`` training form cannot serve this module (and input ``x``); ``None`` when it can."""
         if self.train_reasons is None:
@@ -186,6 +190,9 @@ class HipBackbone(nn.Module):
             return self.train_reasons[0]
         if any(p.requires_grad for m in self._stem_modules() for p in m.parameters()):
             return self.train_reasons[1]
+        extra = self._extra_train_reason()
+        if extra is not None:
+            return extra
         if self.compute_dtype not in (torch.float32, torch.bfloat16):
             return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
         if x is not None and x.requires_grad:
@@ -268,6 +275,32 @@ class HipBackbone(nn.Module):
                 w, b = w * g, b * g
             return w.contiguous(), b.contiguous()
         return derived(norm, "rows_affine", (norm.weight, norm.bias, scale), build)
+
+    def _packed_rows_dgrad(self, layer: nn.Module, scale: Optional[Tensor] = None) -> Tensor:
+        """The backward-data planes (``sdetr_backbone_pack_dgrad``, kernel 1) of a Linear's ``[out, in]`` weight, ``scale``
+        (the layer scale) folded per output; of the 2x2 down-sampler conv, its weight as ``[out, (ky, kx, in)]`` rows."""
+        precision, lib = self._precision(), self._lib()
+        w = layer.weight
+
+        def build():
+            w32 = w.detach().to(torch.float32)
+            if w32.dim() == 4:
+                w32 = w32.permute(0, 2, 3, 1)
+            w32 = w32.reshape(w.shape[0], -1).contiguous()
+            co, ci = w32.shape
+            gamma = torch.ones(co, device=w.device) if scale is None else scale.detach().to(torch.float32).reshape(co).contiguous()
+            ones = torch.ones(co, device=w.device)
+            packed = torch.empty(lib.sdetr_backbone_dgrad_packed_bytes(co, ci, 1, precision) // 2, dtype=torch.int16,
+                                 device=w.device)
+            unused = torch.empty(co, dtype=torch.float32, device=w.device)
+            _hip.launch("sdetr_backbone_pack_dgrad", lib, w.device, w32.data_ptr(), gamma.data_ptr(), ones.data_ptr(), 0.0, co,
+                        ci, 1, precision, packed.data_ptr(), unused.data_ptr(), what=f"{type(self).__name__} (pack dgrad)")
+            return packed
+        return derived(layer, "rows_packed_dgrad", (w, scale), build, extra=(precision, self.compute_dtype))
+
+    def _f32(self, owner, name: str, t: Tensor) -> Tensor:
+        """A parameter as a contiguous fp32 tensor, cached per version."""
+        return derived(owner, "rows_f32_" + name, (t,), lambda: t.detach().to(torch.float32).contiguous().clone())
 
     def _run_plan(self, struct_type, c_prefix: str, ops: list, device) -> None:
         """Launch ``ops`` in order: ``<c_prefix>_run`` over a workspace of ``<c_prefix>_workspace_bytes``."""

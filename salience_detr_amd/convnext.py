@@ -359,32 +359,6 @@ class ConvNeXtBackbone(HipBackbone):
         drew, in forward order; blocks with ``p == 0`` or in ``eval()`` draw nothing.  Valid as ``saved_activations``."""
         return dict(self._train_state()["factors"])
 
-    def _packed_dgrad(self, layer: nn.Module, scale: Optional[Tensor] = None) -> Tensor:
-        """The backward-data planes (``sdetr_backbone_pack_dgrad``, kernel 1) of a Linear's ``[out, in]`` weight, ``scale``
-        (the layer scale) folded per output; of the 2x2 down-sampler conv, its weight as ``[out, (ky, kx, in)]`` rows."""
-        precision, lib = self._precision(), self._lib()
-        w = layer.weight
-
-        def build():
-            w32 = w.detach().to(torch.float32)
-            if w32.dim() == 4:
-                w32 = w32.permute(0, 2, 3, 1)
-            w32 = w32.reshape(w.shape[0], -1).contiguous()
-            co, ci = w32.shape
-            gamma = torch.ones(co, device=w.device) if scale is None else scale.detach().to(torch.float32).reshape(co).contiguous()
-            ones = torch.ones(co, device=w.device)
-            packed = torch.empty(lib.sdetr_backbone_dgrad_packed_bytes(co, ci, 1, precision) // 2, dtype=torch.int16,
-                                 device=w.device)
-            unused = torch.empty(co, dtype=torch.float32, device=w.device)
-            _hip.launch("sdetr_backbone_pack_dgrad", lib, w.device, w32.data_ptr(), gamma.data_ptr(), ones.data_ptr(), 0.0, co,
-                        ci, 1, precision, packed.data_ptr(), unused.data_ptr(), what="ConvNeXtBackbone (pack dgrad)")
-            return packed
-        return derived(layer, "convnext_packed_dgrad", (w, scale), build, extra=(precision, self.compute_dtype))
-
-    def _f32(self, owner, name: str, t: Tensor) -> Tensor:
-        """A parameter as a contiguous fp32 tensor, cached per version."""
-        return derived(owner, "convnext_f32_" + name, (t,), lambda: t.detach().to(torch.float32).contiguous().clone())
-
     def _backward_ops(self, acts: Dict[str, Tensor], factors: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]],
                       splits: int = 0):
         """The backward of one forward as ``(ops, names, grads, keep)``: ``ops`` the ``sdetr_convnext_bwd_op`` list in run
@@ -478,7 +452,7 @@ class ConvNeXtBackbone(HipBackbone):
                         grads[name + ".layer_scale"] = dg.view(c, 1, 1)
                 if not (below or want(dw.weight, dw.bias, norm.weight, norm.bias, fc1.weight, fc1.bias)):
                     continue
-                packed2 = self._packed_dgrad(fc2, m.layer_scale)
+                packed2 = self._packed_rows_dgrad(fc2, m.layer_scale)
                 dh = tmp("dh", (batch, h, w, 4 * c), act)
                 pb.op(name + ".block.5 (dgrad)", 0, dz=dzs.data_ptr(), weight=packed2.data_ptr(), out=dh.data_ptr(),
                       channels=4 * c, height=h, width=w, out_channels=c)
@@ -495,7 +469,7 @@ class ConvNeXtBackbone(HipBackbone):
                 keep.append(packed2)
                 if not (below or want(dw.weight, dw.bias, norm.weight, norm.bias)):
                     continue
-                packed1 = self._packed_dgrad(fc1)
+                packed1 = self._packed_rows_dgrad(fc1)
                 keep.append(packed1)
                 dn = tmp("dn", (batch, h, w, c), act)
                 pb.op(name + ".block.3 (dgrad)", 0, dz=dh.data_ptr(), weight=packed1.data_ptr(), out=dn.data_ptr(), channels=c,
@@ -539,7 +513,7 @@ class ConvNeXtBackbone(HipBackbone):
                     grads[name + ".1.weight"] = dwp.view(co, 2, 2, c).permute(0, 3, 1, 2)
                 dy_next = None
                 if below or want(norm.weight, norm.bias):
-                    packed = self._packed_dgrad(conv)
+                    packed = self._packed_rows_dgrad(conv)
                     keep.append(packed)
                     dpatch = tmp("dpatch", (batch, ho, wo, 4 * c), act)
                     pb.op(name + ".1 (dgrad)", 0, dz=dzc.data_ptr(), weight=packed.data_ptr(), out=dpatch.data_ptr(),

@@ -13,6 +13,8 @@
 //                             ONE k-step); fp32: v_mfma_f32_16x16x4_f32 on fp32 operands -- S never touches LDS
 //   swin_merge_ln_kernel      the 2 x 2 gather of a patch merging + LayerNorm over 4 C, one wave per output row (its own
 //                             gather, the shared row statistics and write)
+// A training forward (swin_backward.hip is its backward) sets `aux` / `row_scale`: fc1 also stores its values before the GELU
+// (EPI 6), proj / fc2 multiply by the branch's stochastic-depth factor per sample before the residual (EPI 7).
 // The row LayerNorm, the host checks of a rows op and the plan entry points are backbone_rows_core.h's.
 // No atomics; every launch writes every element of its outputs.
 #include "backbone_rows_core.h"
@@ -258,14 +260,18 @@ int make_gemm(const sdetr_swin_op &o, int precision, BConv &c)
         return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
     if (o.kind != 0 && (o.residual || o.out_nchw || o.x_nchw || o.kernel_size != 1))
         return fail("%s: only the linear epilogue takes a residual / the NCHW canvas / a patch / writes the NCHW copy", what);
-    if (!all_aligned16(o.x, o.weight, o.bias, o.out, o.residual, o.out_nchw))
+    if (!all_aligned16(o.x, o.weight, o.bias, o.out, o.residual, o.out_nchw, o.aux, o.row_scale))
         return fail("%s: tensors must be 16-byte aligned", what);
+    if ((o.kind != 1 && o.aux) || (o.kind != 0 && o.row_scale))
+        return fail("%s: aux belongs to the GELU epilogue (kind 1), row_scale to the linear one (kind 0)", what);
     if (o.height < o.kernel_size || o.width < o.kernel_size) return fail("%s: empty output", what);
     const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
                         o.kernel_size, o.stride, 0, out_hw(o.height, o.kernel_size, o.stride, 0),
                         out_hw(o.width, o.kernel_size, o.stride, 0), o.x_nchw, o.splits};
     if (int rc = fill_conv(what, g, precision, c)) return rc;
     c.out_nchw = o.out_nchw;
+    c.aux = reinterpret_cast<char *>(o.aux);
+    c.q = o.row_scale;
     return 0;
 }
 
@@ -278,8 +284,10 @@ int run_gemm(hipStream_t s, const sdetr_swin_op &o, int precision, void *ws, int
                     (long long)conv_workspace(c));
     c.partial = reinterpret_cast<float *>(ws);
     const bool x3 = precision == 0;
-    if (o.kind == 1) launch_rows_gemm<1>(s, c, x3);
+    if (o.kind == 1 && o.aux) launch_rows_gemm<6>(s, c, x3);
+    else if (o.kind == 1) launch_rows_gemm<1>(s, c, x3);
     else if (o.kind == 2) launch_rows_gemm<5>(s, c, x3);
+    else if (o.row_scale) launch_gemm<7>(s, c, x3, o.x_nchw != 0);
     else launch_gemm<2>(s, c, x3, o.x_nchw != 0);
     return check_launch("sdetr_swin (GEMM)");
 }
@@ -387,6 +395,8 @@ int check_op(const sdetr_swin_op &o, int precision, int64_t &need)
         need = conv_workspace(c);
         return 0;
     }
+    if (o.kind >= 3 && o.kind <= 5 && (o.aux || o.row_scale))
+        return fail("sdetr_swin: aux / row_scale belong to the GEMM kinds (got kind %d)", o.kind);
     if (o.kind == 3) return check_ln(o, precision);
     if (o.kind == 4) {
         SwAttn a;

@@ -22,10 +22,22 @@ How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/
     returned stage also writes the fp32 NCHW map;
   * patch merging: the 2x2 gather + LayerNorm(4C) in one launch, then the ``reduction`` GEMM.
 ``set_dtype(bfloat16 | float16)`` takes one 16-bit product with fp32 accumulation and 16-bit rows between launches;
-LayerNorm and softmax statistics and the stream stay fp32.  A call with grad enabled on something that requires grad
-takes the plain-torch composite, which is the autograd path; a Swin backward in HIP is out of scope.  Explicit arguments
-with a window other than 7 / 12 or a head dimension other than 32 run the composite too (``hip_form()`` is False).  A CPU
-tensor on the HIP form raises: the hot path has no CPU fallback.
+LayerNorm and softmax statistics and the stream stay fp32.  By default a call with grad enabled on something that
+requires grad takes the plain-torch composite, which is the default autograd path.  Explicit arguments with a window other
+than 7 / 12 or a head dimension other than 32 run the composite too (``hip_form()`` is False).  A CPU tensor on the HIP
+form raises: the hot path has no CPU fallback.
+
+Training in HIP (``set_train_form("hip")``, ``csrc/swin_backward.hip``; the interface and its autograd node are
+``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored state and ``_run_backward``): a forward that
+needs autograd runs the same plan inside one autograd node.  Every block from the lowest trainable module on gets buffers
+of its own (the stream at its input and after the attention branch, both LayerNorm outputs, the qkv rows, the attention
+rows, the values before the GELU and after it), fc1 also stores its pre-GELU values (``aux``) and proj / fc2 multiply by
+the branch's stochastic-depth factor per sample (``row_scale``; two draws per block, on the device, exactly as
+``StochasticDepth`` draws them).  The backward is one ``sdetr_swin_bwd_run`` call over ``_backward_ops``: it stops below
+the lowest trainable module and returns fp32 gradients for the parameters that require them, the relative position bias
+tables included.  Served: ``hip_form()`` with a frozen stem, ``dropout == attention_dropout == 0``, an input without
+gradient, float32 or bfloat16.  The stem's backward, a gradient to the image and float16 training are out of scope;
+anything else raises at forward.
 """
 from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -311,25 +323,44 @@ class SwinBackbone(HipBackbone):
         sources = (attn.relative_position_bias_table, attn.relative_position_index, attn.qkv.bias)
         return derived(attn, "swin_attention", sources, build)
 
-    def build_plan(self, x: Tensor, splits: int = 0):
+    def build_plan(self, x: Tensor, splits: int = 0, train: Optional[dict] = None):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
         ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op.
-        The buffers of a stage are shared by its blocks (the launches of a plan run in order on one stream)."""
+        In inference the buffers of a stage are shared by its blocks (the launches of a plan run in order on one stream).
+        ``train`` (a dict with ``"first"``, the index in ``_sequence()`` of the lowest module whose backward will run): a
+        training forward; every module from there on gets buffers of its own, and ``train`` receives ``"acts"`` (what the
+        backward reads, by name, see ``saved_activations``) and ``"factors"`` (the stochastic-depth factors ``[B]`` of
+        every branch that drew some, by ``<block>.attn`` / ``<block>.mlp``)."""
         act = self.compute_dtype if self._precision() == 1 else torch.float32
         batch = x.shape[0]
         pb = PlanBuilder(_hip.SwinOpStruct, x, batch=batch, height=1, width=1, kernel_size=1, stride=1, splits=splits)
         new, op, keep, outputs = pb.new, pb.op, pb.keep, pb.outputs
+        acts: Dict[str, Tensor] = {}
+        factors: Dict[str, Tensor] = {}
+        if train is not None:
+            train["acts"], train["factors"] = acts, factors
+        index = 0   # of the current module in _sequence()
 
-        def gemm(name, kind, layer, src, out, h, w, layout=0, residual=None, nchw=None):
+        def gemm(name, kind, layer, src, out, h, w, layout=0, residual=None, nchw=None, aux=None, row_scale=None):
             packed, bias = self._packed(layer, layout)
             keep.extend((packed, bias))
             k = layer.kernel_size[0] if isinstance(layer, nn.Conv2d) else 1
             op(name, kind, x=src.data_ptr(), weight=packed.data_ptr(), bias=bias.data_ptr(), residual=_hip.ptr(residual),
                out=out.data_ptr(), out_nchw=_hip.ptr(nchw), in_channels=layer.weight.shape[1], height=h, width=w,
-               out_channels=bias.numel(), kernel_size=k, stride=k, x_nchw=layout)
+               out_channels=bias.numel(), kernel_size=k, stride=k, x_nchw=layout, aux=_hip.ptr(aux),
+               row_scale=_hip.ptr(row_scale))
 
         def layer_norm(name, norm, src, out, h, w, c, out_f32=False):
             pb.layer_norm(name, 3, self._affine(norm), norm.eps, src, out, h, w, c, out_f32)
+
+        def draw(sd):   # StochasticDepth.forward's own draw, in its order
+            if train is None or not sd.training or sd.p == 0.0:
+                return None
+            factor = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=x.device).bernoulli_(1.0 - sd.p)
+            if sd.p < 1.0:
+                factor.div_(1.0 - sd.p)
+            keep.append(factor)
+            return factor
 
         stem = self.body.features[0]
         patch, c = stem[0].kernel_size[0], stem[0].out_channels
@@ -350,20 +381,37 @@ class SwinBackbone(HipBackbone):
             for j, blk in enumerate(blocks):
                 prefix = f"0.features.{2 * i + 1}.{j}"
                 at = blk.attn
-                layer_norm(prefix + ".norm1", blk.norm1, stream, a_in, h, w, c)
-                gemm(prefix + ".attn.qkv", 2, at.qkv, a_in, qkv, h, w)
+                stored = train is not None and train["first"] is not None and index >= train["first"]
+                if stored:   # buffers of the block's own: the backward reads them
+                    a1, a2, qkv_b, att_b = new(rows + (c,), act), new(rows + (c,), act), new(rows + (3 * c,), act), new(rows + (c,), act)
+                    pre, mid_b = new(rows + (hidden,), act), new(rows + (hidden,), act)
+                    x_in, x_mid, x_out = stream, new(rows + (c,), torch.float32), new(rows + (c,), torch.float32)
+                else:
+                    a1 = a2 = a_in
+                    qkv_b, att_b, pre, mid_b = qkv, a_att, None, mid
+                    x_in = x_mid = x_out = stream
+                f_attn, f_mlp = draw(blk.stochastic_depth), draw(blk.stochastic_depth)
+                if f_attn is not None:
+                    factors[prefix + ".attn"], factors[prefix + ".mlp"] = f_attn.view(batch), f_mlp.view(batch)
+                layer_norm(prefix + ".norm1", blk.norm1, x_in, a1, h, w, c)
+                gemm(prefix + ".attn.qkv", 2, at.qkv, a1, qkv_b, h, w)
                 table, qkv_bias = self._attention_operands(at)
                 keep.extend((table, qkv_bias))
-                op(prefix + ".attn", 4, x=qkv.data_ptr(), bias=qkv_bias.data_ptr(), table=table.data_ptr(), out=a_att.data_ptr(),
+                op(prefix + ".attn", 4, x=qkv_b.data_ptr(), bias=qkv_bias.data_ptr(), table=table.data_ptr(), out=att_b.data_ptr(),
                    in_channels=c, height=h, width=w, out_channels=c, window=at.window_size[0], shift=at.shift_size[0],
                    heads=at.num_heads)
-                gemm(prefix + ".attn.proj", 0, at.proj, a_att, stream, h, w, residual=stream)
-                layer_norm(prefix + ".norm2", blk.norm2, stream, a_in, h, w, c)
-                gemm(prefix + ".mlp.0", 1, blk.mlp[0], a_in, mid, h, w)
+                gemm(prefix + ".attn.proj", 0, at.proj, att_b, x_mid, h, w, residual=x_in, row_scale=f_attn)
+                layer_norm(prefix + ".norm2", blk.norm2, x_mid, a2, h, w, c)
+                gemm(prefix + ".mlp.0", 1, blk.mlp[0], a2, mid_b, h, w, aux=pre)
                 nchw = None
                 if j == len(blocks) - 1 and i in self.return_indices:
                     nchw = outputs[f"features.{2 * i + 1}"] = new((batch, c, h, w), torch.float32)
-                gemm(prefix + ".mlp.3", 0, blk.mlp[3], mid, stream, h, w, residual=stream, nchw=nchw)
+                gemm(prefix + ".mlp.3", 0, blk.mlp[3], mid_b, x_out, h, w, residual=x_mid, nchw=nchw, row_scale=f_mlp)
+                if stored:
+                    acts.update({prefix + ".in": x_in, prefix + ".norm1": a1, prefix + ".attn.qkv": qkv_b, prefix + ".attn": att_b,
+                                 prefix + ".mid": x_mid, prefix + ".norm2": a2, prefix + ".mlp.0": pre, prefix + ".mlp.1": mid_b})
+                stream = x_out
+                index += 1
             if merging is not None:
                 prefix = f"0.features.{2 * i + 2}"
                 ho, wo = (h + 1) // 2, (w + 1) // 2
@@ -372,13 +420,18 @@ class SwinBackbone(HipBackbone):
                 keep.extend((gamma, beta))
                 op(prefix + ".norm", 5, x=stream.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(),
                    out=gathered.data_ptr(), in_channels=c, height=h, width=w, out_channels=4 * c, eps=float(merging.norm.eps))
+                if train is not None and train["first"] is not None and index >= train["first"]:
+                    acts.update({prefix + ".in": stream, prefix + ".norm": gathered})
                 stream = new((batch, ho, wo, 2 * c), torch.float32)
                 gemm(prefix + ".reduction", 0, merging.reduction, gathered, stream, ho, wo)
                 h, w, c = ho, wo, 2 * c
+                index += 1
         outputs = {f"features.{2 * i + 1}": outputs[f"features.{2 * i + 1}"] for i in self.return_indices}
         return pb.ops, outputs, keep, pb.names
 
-    def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
+    def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
+        """``state`` (a dict): a training forward; it receives ``"first"``, ``"acts"`` and ``"factors"``, see
+        ``build_plan``."""
         if x.dtype != torch.float32:
             x = x.float()
         _hip.require_device("SwinBackbone", x=x)
@@ -388,6 +441,241 @@ class SwinBackbone(HipBackbone):
             raise RuntimeError(f"SwinBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
         if not self.hip_form():
             raise RuntimeError("SwinBackbone: this configuration has no HIP form (window 7 / 12, head dimension 32)")
-        ops, outputs, keep, _ = self.build_plan(x, splits)
+        if state is not None:
+            state["first"] = self._first_trainable()
+        ops, outputs, keep, _ = self.build_plan(x, splits, state)
         self._run_plan(_hip.SwinOpStruct, "sdetr_swin", ops, x.device)
         return outputs
+
+    # ------------------------------------------------------------------------------------------ training in HIP
+    # (the interface is HipBackbone's: the node keeps the activations the backward reads; its backward is one
+    # ``sdetr_swin_bwd_run`` call over ``_backward_ops`` and returns the fp32 parameter gradients)
+    train_reasons = ("the architecture is not one the HIP kernels serve (a window other than 7 / 12, a head dimension other "
+                     "than 32, a width that is no multiple of 32, a norm other than nn.LayerNorm)",
+                     "the stem (patch embedding and its LayerNorm, features.0) is trainable and has no HIP backward: freeze "
+                     "it with freeze_indices")
+
+    def _stem_modules(self):
+        return (self.body.features[0],)
+
+    def _extra_train_reason(self) -> Optional[str]:
+        for _, blocks, _ in self._stages():
+            for blk in blocks:
+                drops = [blk.attn.attention_dropout, blk.attn.dropout] + [m.p for m in blk.mlp if isinstance(m, nn.Dropout)]
+                if any(p != 0.0 for p in drops):
+                    return "dropout / attention_dropout other than 0 is not served (the reference trains with 0)"
+        return None
+
+    def _output_name(self, i: int) -> str:
+        return f"features.{2 * i + 1}"
+
+    def _sequence(self) -> List[Tuple[str, str, nn.Module]]:
+        """``(kind, name, module)`` of every block (``"block"``) and merging layer (``"merge"``) in forward order."""
+        seq = []
+        for i, blocks, merging in self._stages():
+            seq.extend(("block", f"0.features.{2 * i + 1}.{j}", blk) for j, blk in enumerate(blocks))
+            if merging is not None:
+                seq.append(("merge", f"0.features.{2 * i + 2}", merging))
+        return seq
+
+    def _first_trainable(self) -> Optional[int]:
+        """The index in ``_sequence()`` of the lowest module with a trainable parameter: where the backward stops."""
+        for idx, (_, _, m) in enumerate(self._sequence()):
+            if any(p.requires_grad for p in m.parameters()):
+                return idx
+        return None
+
+    def _trainable(self) -> List[Tuple[str, nn.Parameter]]:
+        return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+
+    def saved_activations(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): what the last ``"hip"`` training forward stored, by name.  Of a block: ``<block>.in`` and
+        ``.mid`` (the fp32 stream at its input and after the attention branch), ``.norm1`` / ``.norm2`` (the LayerNorm
+        outputs), ``.attn.qkv`` (the qkv rows), ``.attn`` (the attention rows), ``.mlp.0`` (before the GELU), ``.mlp.1``
+        (after it); of a merging layer ``<merging>.in`` (the stream it reads) and ``.norm`` (the gathered LayerNorm rows).
+        Valid while that forward's autograd graph is alive."""
+        return dict(self._train_state()["acts"])
+
+    def stochastic_depth_factors(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): ``{<block>.attn | <block>.mlp: factors [B]}`` (0 or 1 / (1 - p)) the last ``"hip"``
+        training forward drew, in forward order (the attention branch, then the MLP branch); blocks with ``p == 0`` or in
+        ``eval()`` draw nothing.  Valid as ``saved_activations``."""
+        return dict(self._train_state()["factors"])
+
+    def _table_pairs(self, attn: ShiftedWindowAttention) -> Tuple[Tensor, Tensor]:
+        """The (query, key) pairs of every table entry as a CSR list: ``(order int32 [N * N], offsets int32 [entries + 1])``."""
+        def build():
+            index = attn.relative_position_index.detach().reshape(-1).to(torch.int64)
+            entries = attn.relative_position_bias_table.shape[0]
+            order = torch.argsort(index, stable=True).to(torch.int32).contiguous()
+            counts = torch.bincount(index, minlength=entries)
+            offsets = torch.zeros(entries + 1, dtype=torch.int64, device=index.device)
+            offsets[1:] = torch.cumsum(counts, 0)
+            return order, offsets.to(torch.int32).contiguous()
+        return derived(attn, "swin_table_pairs", (attn.relative_position_index, attn.relative_position_bias_table), build)
+
+    def _backward_ops(self, acts: Dict[str, Tensor], factors: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]],
+                      splits: int = 0):
+        """The backward of one forward as ``(ops, names, grads, keep)``: ``ops`` the ``sdetr_swin_bwd_op`` list in run order,
+        ``names`` one label per op, ``grads`` ``{parameter name: fp32 gradient}`` (as views of what the ops write), ``keep``
+        every tensor the ops point into.  Walks ``_sequence()`` from the top down to the lowest trainable module."""
+        batch, _, height, width = shape
+        seq, first = self._sequence(), self._first_trainable()
+        act = torch.float32 if self._precision() == 0 else self.compute_dtype
+        anchor = next(iter(acts.values()))
+        dev = anchor.device
+        pb = PlanBuilder(_hip.SwinBwdOpStruct, anchor, batch=batch, splits=splits)
+        new, keep = pb.new, pb.keep
+        scratch: Dict[tuple, Tensor] = {}
+        grads: Dict[str, Tensor] = {}
+
+        def tmp(tag, shape_, dtype):   # a buffer the next block may overwrite: the plan runs in order on one stream
+            key = (tag, tuple(shape_), dtype)
+            if key not in scratch:
+                scratch[key] = new(shape_, dtype)
+            return scratch[key]
+
+        def ones(n):
+            key = ("ones", n)
+            if key not in scratch:
+                scratch[key] = torch.ones(n, device=dev)
+                keep.append(scratch[key])
+            return scratch[key]
+
+        def want(*params):
+            return any(p is not None and p.requires_grad for p in params)
+
+        def linear_bwd(name, layer, dz, x, out, ci, co, h, w):   # dW = dz^T x; out (or None) = dz W
+            if want(layer.weight):
+                dw = new((co, ci), torch.float32)
+                pb.op(name + " (wgrad)", 1, dz=dz.data_ptr(), x=x.data_ptr(), scale=ones(co).data_ptr(), out=dw.data_ptr(),
+                      channels=ci, height=h, width=w, out_channels=co)
+                grads[name + ".weight"] = dw
+            if out is not None:
+                packed = self._packed_rows_dgrad(layer)
+                keep.append(packed)
+                pb.op(name + " (dgrad)", 0, dz=dz.data_ptr(), weight=packed.data_ptr(), out=out.data_ptr(), channels=ci, height=h,
+                      width=w, out_channels=co)
+
+        def rows(name, dy_, factor, out, bias, c, h, w):   # out = factor[n] * dy in the compute dtype, the bias gradient
+            db = new((c,), torch.float32) if want(bias) else None
+            pb.op(name + " (rows)", 2, dz=dy_.data_ptr(), scale=_hip.ptr(factor), out=out.data_ptr(), dbias=_hip.ptr(db), channels=c,
+                  height=h, width=w)
+            return db
+
+        def norm_grads(name, norm, kind, **fields):   # a LayerNorm backward (kind 4, or 8 over the merging gather)
+            gamma = self._f32(norm, "weight", norm.weight)
+            keep.append(gamma)
+            affine = want(norm.weight, norm.bias)
+            n = norm.weight.numel()
+            dgam = new((n,), torch.float32) if affine else None
+            dbet = new((n,), torch.float32) if affine else None
+            pb.op(name + (" (layer norm)" if kind == 4 else " (merging)"), kind, gamma=gamma.data_ptr(), dgamma=_hip.ptr(dgam),
+                  dbeta=_hip.ptr(dbet), eps=float(norm.eps), **fields)
+            if want(norm.weight):
+                grads[name + ".weight"] = dgam
+            if want(norm.bias):
+                grads[name + ".bias"] = dbet
+
+        # the size and width of every module's input
+        patch = self.body.features[0][0].kernel_size[0]
+        sizes, h, w, c = [], height // patch, width // patch, self.body.features[0][0].out_channels
+        for kind, _, _ in seq:
+            sizes.append((h, w, c))
+            if kind == "merge":
+                h, w, c = (h + 1) // 2, (w + 1) // 2, 2 * c
+        last_of = {f"0.features.{2 * i + 1}.{len(blocks) - 1}": i for i, blocks, _ in self._stages()}
+        merge_of = {f"0.features.{2 * i + 2}": i for i, _, merging in self._stages() if merging is not None}
+
+        def ingest(name, stage, dy_, c, h, w):   # the returned map's cotangent (+ what arrives from above) as fp32 rows
+            g = cotangents.get(f"features.{2 * stage + 1}")
+            if g is None and dy_ is not None:
+                return dy_
+            g = torch.zeros((batch, c, h, w), device=dev) if g is None else g.to(torch.float32).contiguous()
+            keep.append(g)
+            out = new((batch, h, w, c), torch.float32)
+            pb.op(name + " (ingest)", 5, dz=g.data_ptr(), add=_hip.ptr(dy_), out=out.data_ptr(), channels=c, height=h, width=w)
+            return out
+
+        dy, flip = None, 0
+        for idx in range(len(seq) - 1, (first if first is not None else len(seq)) - 1, -1):
+            kind, name, m = seq[idx]
+            h, w, c = sizes[idx]
+            below = idx > first
+            if kind == "merge":
+                stage = merge_of[name]
+                ho, wo = (h + 1) // 2, (w + 1) // 2
+                dzr = tmp("dzr", (batch, ho, wo, 2 * c), act)
+                rows(name + ".reduction", dy, None, dzr, None, 2 * c, ho, wo)
+                dgath = tmp("dgath", (batch, ho, wo, 4 * c), act)
+                linear_bwd(name + ".reduction", m.reduction, dzr, acts[name + ".norm"], dgath, 4 * c, 2 * c, ho, wo)
+                add = ingest(name, stage, None, c, h, w) if stage in self.return_indices else None
+                dx = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
+                flip ^= 1
+                norm_grads(name + ".norm", m.norm, 8, dz=dgath.data_ptr(), x=acts[name + ".in"].data_ptr(), add=_hip.ptr(add),
+                           out=dx.data_ptr(), channels=c, height=h, width=w)
+                dy = dx
+                continue
+            stage = last_of.get(name)
+            if stage is not None and stage in self.return_indices and f"0.features.{2 * stage + 2}" not in merge_of:
+                dy = ingest(name, stage, dy, c, h, w)
+            at, fc1, fc2 = m.attn, m.mlp[0], m.mlp[3]
+            hidden = fc1.out_features
+            # the MLP branch
+            dzs = tmp("dzs", (batch, h, w, c), act)
+            db = rows(name + ".mlp.3", dy, factors.get(name + ".mlp"), dzs, fc2.bias, c, h, w)
+            if db is not None:
+                grads[name + ".mlp.3.bias"] = db
+            dh = tmp("dh", (batch, h, w, hidden), act)
+            linear_bwd(name + ".mlp.3", fc2, dzs, acts[name + ".mlp.1"], dh, hidden, c, h, w)
+            db1 = new((hidden,), torch.float32) if want(fc1.bias) else None
+            pb.op(name + ".mlp.1 (gelu)", 3, dz=dh.data_ptr(), x=acts[name + ".mlp.0"].data_ptr(), out=dh.data_ptr(),
+                  dbias=_hip.ptr(db1), channels=hidden, height=h, width=w)
+            if db1 is not None:
+                grads[name + ".mlp.0.bias"] = db1
+            dn = tmp("dn", (batch, h, w, c), act)
+            linear_bwd(name + ".mlp.0", fc1, dh, acts[name + ".norm2"], dn, c, hidden, h, w)
+            dmid = tmp("dmid", (batch, h, w, c), torch.float32)
+            norm_grads(name + ".norm2", m.norm2, 4, dz=dn.data_ptr(), x=acts[name + ".mid"].data_ptr(), add=dy.data_ptr(),
+                       out=dmid.data_ptr(), channels=c, height=h, width=w)
+            # the attention branch
+            db = rows(name + ".attn.proj", dmid, factors.get(name + ".attn"), dzs, at.proj.bias, c, h, w)
+            if db is not None:
+                grads[name + ".attn.proj.bias"] = db
+            datt = tmp("datt", (batch, h, w, c), act)
+            linear_bwd(name + ".attn.proj", at.proj, dzs, acts[name + ".attn"], datt, c, c, h, w)
+            table, qkv_bias = self._attention_operands(at)
+            order, offsets = self._table_pairs(at)
+            keep.extend((table, qkv_bias, order, offsets))
+            dqkv, dpad = tmp("dqkv", (batch, h, w, 3 * c), act), tmp("dpad", (3 * c,), torch.float32)
+            dtable = new(tuple(at.relative_position_bias_table.shape), torch.float32) if want(at.relative_position_bias_table) else None
+            pb.op(name + ".attn (attention)", 6, x=acts[name + ".attn.qkv"].data_ptr(), dz=datt.data_ptr(), bias=qkv_bias.data_ptr(),
+                  table=table.data_ptr(), order=order.data_ptr(), offsets=offsets.data_ptr(), out=dqkv.data_ptr(),
+                  dbias=dpad.data_ptr(), dtable=_hip.ptr(dtable), channels=c, height=h, width=w, window=at.window_size[0],
+                  shift=at.shift_size[0], heads=at.num_heads)
+            if dtable is not None:
+                grads[name + ".attn.relative_position_bias_table"] = dtable
+            if want(at.qkv.bias):
+                dbq = new((3 * c,), torch.float32)
+                pb.op(name + ".attn.qkv (bias)", 7, dz=dqkv.data_ptr(), add=dpad.data_ptr(), dbias=dbq.data_ptr(), channels=3 * c,
+                      height=h, width=w)
+                grads[name + ".attn.qkv.bias"] = dbq
+            linear_bwd(name + ".attn.qkv", at.qkv, dqkv, acts[name + ".norm1"], dn, c, 3 * c, h, w)
+            # (the lowest block still needs norm1's dgamma / dbeta; its input gradient lands in a buffer nobody reads)
+            dx = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
+            flip ^= 1
+            norm_grads(name + ".norm1", m.norm1, 4, dz=dn.data_ptr(), x=acts[name + ".in"].data_ptr(), add=dmid.data_ptr(),
+                       out=dx.data_ptr(), channels=c, height=h, width=w)
+            dy = dx if below else None
+        return pb.ops, pb.names, grads, keep
+
+    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
+                      ) -> Dict[str, Tensor]:
+        """Runs the backward plan on the stored activations; returns ``{parameter name: fp32 gradient}``."""
+        acts = state["acts"]
+        if not acts:
+            return {}
+        ops, _, grads, keep = self._backward_ops(acts, state["factors"], shape, cotangents, splits)
+        if ops:
+            self._run_plan(_hip.SwinBwdOpStruct, "sdetr_swin_bwd", ops, next(iter(acts.values())).device)
+        return grads
