@@ -372,13 +372,9 @@ class ResNetBackbone(HipBackbone):
 
     def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
         """``state`` (a dict): a training forward; it receives ``"acts"``, see ``build_plan``."""
-        if x.dtype != torch.float32:
-            x = x.float()
-        _hip.require_device("ResNetBackbone", x=x)
-        for t in list(self.parameters()) + list(self.buffers()):
+        x = self._check_image(x)
+        for t in self.buffers():
             _hip.require_device("ResNetBackbone", parameter=t.detach())
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f"ResNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
         acts = None if state is None else state.setdefault("acts", {})
         ops, outputs, keep, _ = self.build_plan(x, splits, acts)
         self._run_plan(_hip.BackboneOpStruct, "sdetr_backbone", ops, x.device)

@@ -1,9 +1,11 @@
 """What the four HIP backbones (``backbone.py``, ``convnext.py``, ``focalnet.py``, ``swin.py``) share: ``HipBackbone``,
 the module base with the precision switch, the torch / HIP dispatch, checkpoint loading, the operand packers, the
-launch of a plan and the training interface (``set_train_form``, ``hip_train_reason``, ``forward_hip_train`` and the one
-autograd node behind it: a backbone with a HIP backward adds its forward's stored state and ``_run_backward``);
-``PlanBuilder``, the op list a ``build_plan`` fills; and the two parameter-free holder modules ``Permute`` and
-``StochasticDepth``."""
+launch of a plan, the opening checks of a ``forward_hip`` and the training interface (``set_train_form``,
+``hip_train_reason``, ``forward_hip_train`` and the one autograd node behind it: a backbone with a HIP backward adds its
+forward's stored state and either ``_sequence`` and ``_backward_ops``, which the default ``_run_backward`` runs, or a
+``_run_backward`` of its own); ``PlanBuilder``, the op list a ``build_plan`` fills, with the stochastic-depth draw;
+``BackwardPlanBuilder``, the op list, gradients, scratch buffers and shared emitters a ``_backward_ops`` fills; and the
+two parameter-free holder modules ``Permute`` and ``StochasticDepth``."""
 import os
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -81,6 +83,114 @@ class PlanBuilder:
         self.op(name, kind, x=src.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=out.data_ptr(), in_channels=c,
                 height=h, width=w, out_channels=c, out_f32=1 if out_f32 else 0, eps=float(eps), **fields)
 
+    def draw(self, sd: StochasticDepth, batch: int, training_forward: bool) -> Optional[Tensor]:
+        """``StochasticDepth.forward``'s own draw, in its order: the factors ``[batch, 1, 1, 1]`` (0 or 1 / (1 - p)) of
+        one residual branch; ``None`` when nothing is drawn (inference, ``eval()`` or ``p == 0``)."""
+        if not training_forward or not sd.training or sd.p == 0.0:
+            return None
+        factor = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=self.device).bernoulli_(1.0 - sd.p)
+        if sd.p < 1.0:
+            factor.div_(1.0 - sd.p)
+        self.keep.append(factor)
+        return factor
+
+
+class BackwardPlanBuilder(PlanBuilder):
+    """The op list of one backward over rows ``[batch, h, w, c]``: ``grads`` (``{parameter name: fp32 tensor}``, as views
+    of what the ops write), the scratch buffers and one emitter per kind that ``sdetr_convnext_bwd_op`` and
+    ``sdetr_swin_bwd_op`` number alike (0 dgrad, 1 wgrad, 2 rows, 3 gelu, 4 layer norm); the NCHW ingest has the caller's
+    number.  An op's name is its label in the op-timing tools."""
+
+    def __init__(self, struct_type, x: Tensor, **defaults):
+        super().__init__(struct_type, x, **defaults)
+        self.grads: Dict[str, Tensor] = {}
+        self.scratch: Dict[tuple, Tensor] = {}
+        self.flip = 0
+
+    def tmp(self, tag: str, shape, dtype) -> Tensor:
+        """A buffer the next block may overwrite: the plan runs in order on one stream."""
+        key = (tag, tuple(shape), dtype)
+        if key not in self.scratch:
+            self.scratch[key] = self.new(shape, dtype)
+        return self.scratch[key]
+
+    def ones(self, n: int) -> Tensor:
+        key = ("ones", n)
+        if key not in self.scratch:
+            self.scratch[key] = torch.ones(n, device=self.device)
+            self.keep.append(self.scratch[key])
+        return self.scratch[key]
+
+    @staticmethod
+    def want(*params) -> bool:
+        return any(p is not None and p.requires_grad for p in params)
+
+    def grad(self, name: str, shape, *params) -> Optional[Tensor]:
+        """The fp32 gradient buffer of parameter ``name`` when one of ``params`` requires it, else ``None``."""
+        if not self.want(*params):
+            return None
+        self.grads[name] = self.new(shape, torch.float32)
+        return self.grads[name]
+
+    def next_dy(self, shape) -> Tensor:
+        """The stream's gradient below the current module: two fp32 buffers in turns."""
+        dy = self.tmp(f"dy{self.flip}", shape, torch.float32)
+        self.flip ^= 1
+        return dy
+
+    def wgrad(self, name: str, dz: Tensor, x: Tensor, ci: int, co: int, h: int, w: int) -> Tensor:
+        """``dW [co, ci] = dz^T x`` of a Linear, registered as ``<name>.weight``."""
+        dw = self.grads[name + ".weight"] = self.new((co, ci), torch.float32)
+        self.op(name + " (wgrad)", 1, dz=dz.data_ptr(), x=x.data_ptr(), scale=self.ones(co).data_ptr(), out=dw.data_ptr(),
+                channels=ci, height=h, width=w, out_channels=co)
+        return dw
+
+    def dgrad(self, name: str, packed: Tensor, dz: Tensor, out: Tensor, ci: int, co: int, h: int, w: int):
+        """``out = dz W`` over the ``_packed_rows_dgrad`` planes of a Linear's weight."""
+        self.keep.append(packed)
+        self.op(name + " (dgrad)", 0, dz=dz.data_ptr(), weight=packed.data_ptr(), out=out.data_ptr(), channels=ci, height=h,
+                width=w, out_channels=co)
+
+    def rows(self, name: str, dz: Tensor, factor: Optional[Tensor], out: Tensor, dbias: Optional[Tensor], c: int, h: int,
+             w: int):
+        """``out = factor[n] * dz`` in ``out``'s type and the column sums of it (a bias gradient) into ``dbias``."""
+        self.op(name + " (rows)", 2, dz=dz.data_ptr(), scale=_hip.ptr(factor), out=out.data_ptr(), dbias=_hip.ptr(dbias),
+                channels=c, height=h, width=w)
+
+    def gelu(self, name: str, dz: Tensor, pre: Tensor, dbias: Optional[Tensor], c: int, h: int, w: int):
+        """``dz *= gelu'(pre)`` in place and the column sums of it (the bias gradient of the Linear in front)."""
+        self.op(name + " (gelu)", 3, dz=dz.data_ptr(), x=pre.data_ptr(), out=dz.data_ptr(), dbias=_hip.ptr(dbias), channels=c,
+                height=h, width=w)
+
+    def layer_norm_bwd(self, name: str, norm: nn.LayerNorm, gamma32: Tensor, kind: int = 4, label: str = " (layer norm)",
+                       **fields):
+        """A LayerNorm backward (kind 4, or a backbone's own variant of it); ``fields`` are the op's remaining ones,
+        tensors for its pointers.  Registers ``<name>.weight`` / ``<name>.bias``."""
+        self.keep.append(gamma32)
+        n = norm.weight.numel()
+        affine = self.want(norm.weight, norm.bias)
+        dgam = self.new((n,), torch.float32) if affine else None
+        dbet = self.new((n,), torch.float32) if affine else None
+        fields = {k: v.data_ptr() if isinstance(v, Tensor) else v for k, v in fields.items()}
+        self.op(name + label, kind, gamma=gamma32.data_ptr(), dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), eps=float(norm.eps),
+                **fields)
+        if self.want(norm.weight):
+            self.grads[name + ".weight"] = dgam
+        if self.want(norm.bias):
+            self.grads[name + ".bias"] = dbet
+
+    def ingest(self, name: str, kind: int, cotangent: Optional[Tensor], add: Optional[Tensor], c: int, h: int, w: int) -> Tensor:
+        """A returned map's NCHW cotangent plus ``add`` (what arrives from above) as fp32 rows; ``add`` itself when the
+        map has no cotangent."""
+        if cotangent is None and add is not None:
+            return add
+        batch = self.defaults["batch"]
+        g = torch.zeros((batch, c, h, w), device=self.device) if cotangent is None else cotangent.to(torch.float32).contiguous()
+        self.keep.append(g)
+        out = self.new((batch, h, w, c), torch.float32)
+        self.op(name + " (ingest)", kind, dz=g.data_ptr(), add=_hip.ptr(add), out=out.data_ptr(), channels=c, height=h, width=w)
+        return out
+
 
 class _TrainState(dict):
     """What one ``"hip"`` training forward stored for its backward; a dict that can be weakly referenced."""
@@ -111,13 +221,19 @@ class HipBackbone(nn.Module):
     (``forward_torch``, the autograd path); a subclass gives both, ``hip_form()`` and ``compute_dtype``.
 
     One with a HIP backward also gives ``train_reasons`` and ``_stem_modules()`` (what ``hip_train_reason`` says in its
-    own words), ``_trainable()`` (``[(name, tensor)]``: the autograd node's inputs), ``_output_name(i)``,
-    ``forward_hip(x, splits, state)`` (``state``, a dict, receives what the backward reads) and
-    ``_run_backward(state, shape, cotangents, splits)`` (``{name: fp32 gradient}``)."""
+    own words), ``_output_name(i)`` and ``forward_hip(x, splits, state)`` (``state``, a dict, receives what the backward
+    reads).  The rest has a default here for a backbone whose backward walks ``_sequence()`` (``[(kind, name, module)]``
+    in forward order) in ``_backward_ops`` (a ``BackwardPlanBuilder``'s ``(ops, names, grads, keep)``), run as
+    ``backward_struct`` ops by ``<backward_prefix>_run``: ``_trainable()`` (``[(name, tensor)]``: the autograd node's
+    inputs), ``_first_trainable()``, the test hooks and ``_run_backward(state, shape, cotangents, splits)`` (``{name:
+    fp32 gradient}``).  The ResNet, whose backward plan goes by tensor names, overrides them."""
 
     train_form = "torch"
     # of a backbone with a HIP backward: why hip_form() is False, why a trainable stem is not served
     train_reasons: Optional[Tuple[str, str]] = None
+    # of the default _run_backward: the backward op struct and the C prefix of its entry points
+    backward_struct = None
+    backward_prefix: Optional[str] = None
 
     @staticmethod
     def _freeze(module: nn.Module):
@@ -222,6 +338,49 @@ class HipBackbone(nn.Module):
         if state is None:
             raise RuntimeError(f"{type(self).__name__}: no 'hip' training forward is alive")
         return state
+
+    def _trainable(self) -> List[Tuple[str, Tensor]]:
+        return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+
+    def _first_trainable(self) -> Optional[int]:
+        """The index in ``_sequence()`` of the lowest module with a trainable parameter: where the backward stops."""
+        for idx, (_, _, m) in enumerate(self._sequence()):
+            if any(p.requires_grad for p in m.parameters()):
+                return idx
+        return None
+
+    def saved_activations(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): what the last ``"hip"`` training forward stored, by name (the backbone's module lists
+        the names next to its ``_sequence``).  Valid while that forward's autograd graph is alive."""
+        return dict(self._train_state()["acts"])
+
+    def stochastic_depth_factors(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): ``{branch name: factors [B]}`` (0 or 1 / (1 - p)) the last ``"hip"`` training forward
+        drew, in forward order; blocks with ``p == 0`` or in ``eval()`` draw nothing.  Valid as ``saved_activations``."""
+        return dict(self._train_state()["factors"])
+
+    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
+                      ) -> Dict[str, Tensor]:
+        """Runs the backward plan on the stored activations; returns ``{parameter name: fp32 gradient}``."""
+        acts = state["acts"]
+        if not acts:
+            return {}
+        ops, _, grads, keep = self._backward_ops(acts, state["factors"], shape, cotangents, splits)
+        if ops:
+            self._run_plan(self.backward_struct, self.backward_prefix, ops, next(iter(acts.values())).device)
+        return grads
+
+    def _check_image(self, x: Tensor) -> Tensor:
+        """The opening checks of every ``forward_hip``: ``x`` as fp32, on the device like every parameter, ``[B, 3, H, W]``."""
+        who = type(self).__name__
+        if x.dtype != torch.float32:
+            x = x.float()
+        _hip.require_device(who, x=x)
+        for t in self.parameters():
+            _hip.require_device(who, parameter=t.detach())
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"{who}: expected [B, 3, H, W], got {tuple(x.shape)}")
+        return x
 
     def _precision(self) -> int:
         return 0 if self.compute_dtype == torch.float32 else 1

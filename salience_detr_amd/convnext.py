@@ -24,9 +24,10 @@ By default a call with grad enabled on something that requires grad takes the pl
 on the HIP form raises: the hot path has no CPU fallback.
 
 Training in HIP (``set_train_form("hip")``, ``csrc/convnext_backward.hip``; the interface and its autograd node are
-``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored state and ``_run_backward``): a forward that
-needs autograd runs the same plan inside one autograd node, with three additions to its launches (``aux`` /
-``row_scale`` of ``sdetr_convnext_op``): the depthwise launch also stores its fp32 values before the LayerNorm, Linear 1
+``backbone_base.HipBackbone``'s, as are ``_trainable``, ``_first_trainable``, the test hooks and ``_run_backward``; this
+module gives ``_sequence``, the stored state and ``_backward_ops``, its own kinds next to the emitters of the base's
+``BackwardPlanBuilder``): a forward that needs autograd runs the same plan inside one autograd node, with three
+additions to its launches (``aux`` / ``row_scale`` of ``sdetr_convnext_op``): the depthwise launch also stores its fp32 values before the LayerNorm, Linear 1
 its values before the GELU, and Linear 2 multiplies by the block's stochastic-depth factor per sample (drawn on the
 device exactly as ``StochasticDepth`` draws it).  The backward is one ``sdetr_convnext_bwd_run`` call over ``_backward_ops``: it stops below the lowest trainable
 module and returns fp32 gradients for the parameters that require them.  Served: ``hip_form()`` with a frozen stem, an
@@ -41,7 +42,8 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import HipBackbone, Permute, PlanBuilder, StochasticDepth  # noqa: F401 (both modules re-exported)
+from .backbone_base import BackwardPlanBuilder, HipBackbone, PlanBuilder
+from .backbone_base import Permute, StochasticDepth  # noqa: F401 (both modules re-exported)
 from .derived import derived
 
 
@@ -265,13 +267,8 @@ class ConvNeXtBackbone(HipBackbone):
                 stored = train is not None and index >= train["first"]
                 pre_norm = new((batch, h, w, c), torch.float32) if stored else None
                 pre_gelu = new((batch, h, w, 4 * c), act) if stored else None
-                factor = None
-                sd = blk.stochastic_depth
-                if train is not None and sd.training and sd.p > 0.0:   # StochasticDepth.forward's own draw, in its order
-                    factor = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=x.device).bernoulli_(1.0 - sd.p)
-                    if sd.p < 1.0:
-                        factor.div_(1.0 - sd.p)
-                    keep.append(factor)
+                factor = pb.draw(blk.stochastic_depth, batch, train is not None)
+                if factor is not None:
                     factors[prefix] = factor.view(batch)
                 pb.op(prefix + ".block.0+2", 2, x=y.data_ptr(), weight=taps.data_ptr(), bias=dw_bias.data_ptr(),
                       gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=rows.data_ptr(), in_channels=c, height=h, width=w,
@@ -300,13 +297,7 @@ class ConvNeXtBackbone(HipBackbone):
     def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
         """``state`` (a dict): a training forward; it receives ``"first"``, ``"acts"`` and ``"factors"``, see
         ``build_plan``."""
-        if x.dtype != torch.float32:
-            x = x.float()
-        _hip.require_device("ConvNeXtBackbone", x=x)
-        for t in self.parameters():
-            _hip.require_device("ConvNeXtBackbone", parameter=t.detach())
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f"ConvNeXtBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
+        x = self._check_image(x)
         if min(x.shape[2], x.shape[3]) < 4 * 2 ** (self.num_stages - 1):
             raise RuntimeError(f"ConvNeXtBackbone: a {tuple(x.shape[2:])} canvas leaves a stage without pixels")
         if state is not None:
@@ -321,6 +312,7 @@ class ConvNeXtBackbone(HipBackbone):
     train_reasons = ("the architecture is not one the HIP kernels serve (a block other than CNBlock with nn.LayerNorm, a "
                      "norm other than LayerNorm2d, or a width that is no multiple of 32 up to 3072)",
                      "the stem (features.0) is not frozen: the 4x4 patchify backward is out of scope")
+    backward_struct, backward_prefix = _hip.ConvnextBwdOpStruct, "sdetr_convnext_bwd"
 
     def _stem_modules(self):
         return (self.features[0],)
@@ -337,27 +329,10 @@ class ConvNeXtBackbone(HipBackbone):
                 seq.append(("down", f"features.{2 * i + 2}", self.features[2 * i + 2]))
         return seq
 
-    def _first_trainable(self) -> Optional[int]:
-        """The index in ``_sequence()`` of the lowest module with a trainable parameter: where the backward stops."""
-        for idx, (_, _, m) in enumerate(self._sequence()):
-            if any(p.requires_grad for p in m.parameters()):
-                return idx
-        return None
-
-    def _trainable(self) -> List[Tuple[str, nn.Parameter]]:
-        return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
-
-    def saved_activations(self) -> Dict[str, Tensor]:
-        """Test hook (read-only): what the last ``"hip"`` training forward stored, by op name: ``<block>.in`` (the block's
-        fp32 input rows), ``<block>.block.0`` (fp32, before the LayerNorm), ``.block.2`` (normalised rows), ``.block.3``
-        (before the GELU), ``.block.4`` (after it), and ``<down>.in`` / ``<down>.0`` of a down-sampler.  Valid while that
-        forward's autograd graph is alive."""
-        return dict(self._train_state()["acts"])
-
-    def stochastic_depth_factors(self) -> Dict[str, Tensor]:
-        """Test hook (read-only): ``{block name: factors [B]}`` (0 or 1 / (1 - p)) the last ``"hip"`` training forward
-        drew, in forward order; blocks with ``p == 0`` or in ``eval()`` draw nothing.  Valid as ``saved_activations``."""
-        return dict(self._train_state()["factors"])
+    # ``saved_activations()`` (HipBackbone's test hook) holds, by op name: ``<block>.in`` (the block's fp32 input rows),
+    # ``<block>.block.0`` (fp32, before the LayerNorm), ``.block.2`` (normalised rows), ``.block.3`` (before the GELU),
+    # ``.block.4`` (after it), and ``<down>.in`` / ``<down>.0`` of a down-sampler; ``stochastic_depth_factors()`` is
+    # ``{block name: factors [B]}``.
 
     def _backward_ops(self, acts: Dict[str, Tensor], factors: Dict[str, Tensor], shape, cotangents: Dict[str, Optional[Tensor]],
                       splits: int = 0):
@@ -367,40 +342,8 @@ class ConvNeXtBackbone(HipBackbone):
         batch, _, height, width = shape
         seq, first = self._sequence(), self._first_trainable()
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
-        dev = next(iter(acts.values())).device
-        pb = PlanBuilder(_hip.ConvnextBwdOpStruct, next(iter(acts.values())), batch=batch, splits=splits)
-        new, keep = pb.new, pb.keep
-        scratch: Dict[tuple, Tensor] = {}
-        grads: Dict[str, Tensor] = {}
-
-        def tmp(tag, shape_, dtype):   # a buffer the next block may overwrite: the plan runs in order on one stream
-            key = (tag, tuple(shape_), dtype)
-            if key not in scratch:
-                scratch[key] = new(shape_, dtype)
-            return scratch[key]
-
-        def ones(n):
-            key = ("ones", n)
-            if key not in scratch:
-                scratch[key] = torch.ones(n, device=dev)
-                keep.append(scratch[key])
-            return scratch[key]
-
-        def want(*params):
-            return any(p is not None and p.requires_grad for p in params)
-
-        def layer_norm_bwd(name, norm, dz, x, out, c, h, w):   # out = the gradient at the LayerNorm's input rows x
-            gamma = self._f32(norm, "weight", norm.weight)
-            keep.append(gamma)
-            affine = want(norm.weight, norm.bias)
-            dgam = new((c,), torch.float32) if affine else None
-            dbet = new((c,), torch.float32) if affine else None
-            pb.op(name + " (layer norm)", 4, dz=dz.data_ptr(), x=x.data_ptr(), gamma=gamma.data_ptr(), out=out.data_ptr(),
-                  dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), channels=c, height=h, width=w, eps=float(norm.eps))
-            if want(norm.weight):
-                grads[name + ".weight"] = dgam
-            if want(norm.bias):
-                grads[name + ".bias"] = dbet
+        pb = BackwardPlanBuilder(self.backward_struct, next(iter(acts.values())), batch=batch, splits=splits)
+        new, keep, tmp, want, grads = pb.new, pb.keep, pb.tmp, pb.want, pb.grads
 
         # the spatial size of every module's input
         sizes, h, w = [], height // 4, width // 4
@@ -410,7 +353,7 @@ class ConvNeXtBackbone(HipBackbone):
                 h, w = h // 2, w // 2
         stage_of = {f"features.{2 * i + 1}.{len(st) - 1}": i for i, st in enumerate(self.stages())}
 
-        dy, flip = None, 0
+        dy = None
         for idx in range(len(seq) - 1, first - 1, -1):
             kind, name, m = seq[idx]
             h, w = sizes[idx]
@@ -419,25 +362,17 @@ class ConvNeXtBackbone(HipBackbone):
                 c = m.block[0].weight.shape[0]
                 stage = stage_of.get(name)
                 if stage is not None and stage in self.return_indices:
-                    g = cotangents.get(f"features.{2 * stage + 1}")
-                    if g is not None or dy is None:
-                        g = torch.zeros((batch, c, h, w), device=dev) if g is None else g.to(torch.float32).contiguous()
-                        keep.append(g)
-                        out = new((batch, h, w, c), torch.float32)
-                        pb.op(name + " (ingest)", 10, dz=g.data_ptr(), add=_hip.ptr(dy), out=out.data_ptr(), channels=c, height=h,
-                              width=w)
-                        dy = out
+                    dy = pb.ingest(name, 10, cotangents.get(f"features.{2 * stage + 1}"), dy, c, h, w)   # kind 10: NCHW ingest
                 dw, norm, fc1, fc2 = m.block[0], m.block[2], m.block[3], m.block[5]
-                factor = factors.get(name)
                 dzs, db2p = tmp("dzs", (batch, h, w, c), act), tmp("db2p", (c,), torch.float32)
-                pb.op(name + " (rows)", 2, dz=dy.data_ptr(), scale=_hip.ptr(factor), out=dzs.data_ptr(), dbias=db2p.data_ptr(),
-                      channels=c, height=h, width=w)
+                pb.rows(name, dy, factors.get(name), dzs, db2p, c, h, w)
                 if want(fc2.weight, fc2.bias, m.layer_scale):
+                    # fc2's products carry the layer scale: kind 7 turns the plain sums into the three gradients
                     dw2p = tmp("dw2p", (c, 4 * c), torch.float32)
                     pb.op(name + ".block.5 (wgrad)", 1, dz=dzs.data_ptr(), x=acts[name + ".block.4"].data_ptr(),
-                          scale=ones(c).data_ptr(), out=dw2p.data_ptr(), channels=4 * c, height=h, width=w, out_channels=c)
-                    dw2 = new((c, 4 * c), torch.float32) if want(fc2.weight) else None
-                    db2 = new((c,), torch.float32) if want(fc2.bias) else None
+                          scale=pb.ones(c).data_ptr(), out=dw2p.data_ptr(), channels=4 * c, height=h, width=w, out_channels=c)
+                    dw2 = pb.grad(name + ".block.5.weight", (c, 4 * c), fc2.weight)
+                    db2 = pb.grad(name + ".block.5.bias", (c,), fc2.bias)
                     dg = new((c,), torch.float32) if want(m.layer_scale) else None
                     w2, b2 = self._f32(fc2, "weight", fc2.weight), self._f32(fc2, "bias", fc2.bias)
                     g32 = self._f32(m, "layer_scale", m.layer_scale)
@@ -445,51 +380,34 @@ class ConvNeXtBackbone(HipBackbone):
                     pb.op(name + " (layer scale)", 7, dz=db2p.data_ptr(), x=dw2p.data_ptr(), weight=w2.data_ptr(),
                           scale=b2.data_ptr(), gamma=g32.data_ptr(), out=_hip.ptr(dw2), dbias=_hip.ptr(db2), dgamma=_hip.ptr(dg),
                           batch=1, channels=c, height=1, width=1, out_channels=4 * c)
-                    for pname, t in ((".block.5.weight", dw2), (".block.5.bias", db2)):
-                        if t is not None:
-                            grads[name + pname] = t
                     if dg is not None:
                         grads[name + ".layer_scale"] = dg.view(c, 1, 1)
                 if not (below or want(dw.weight, dw.bias, norm.weight, norm.bias, fc1.weight, fc1.bias)):
                     continue
-                packed2 = self._packed_rows_dgrad(fc2, m.layer_scale)
                 dh = tmp("dh", (batch, h, w, 4 * c), act)
-                pb.op(name + ".block.5 (dgrad)", 0, dz=dzs.data_ptr(), weight=packed2.data_ptr(), out=dh.data_ptr(),
-                      channels=4 * c, height=h, width=w, out_channels=c)
-                db1 = new((4 * c,), torch.float32) if want(fc1.bias) else None
-                pb.op(name + ".block.4 (gelu)", 3, dz=dh.data_ptr(), x=acts[name + ".block.3"].data_ptr(), out=dh.data_ptr(),
-                      dbias=_hip.ptr(db1), channels=4 * c, height=h, width=w)
-                if db1 is not None:
-                    grads[name + ".block.3.bias"] = db1
+                pb.dgrad(name + ".block.5", self._packed_rows_dgrad(fc2, m.layer_scale), dzs, dh, 4 * c, c, h, w)
+                pb.gelu(name + ".block.4", dh, acts[name + ".block.3"], pb.grad(name + ".block.3.bias", (4 * c,), fc1.bias),
+                        4 * c, h, w)
                 if want(fc1.weight):
-                    dw1 = new((4 * c, c), torch.float32)
-                    pb.op(name + ".block.3 (wgrad)", 1, dz=dh.data_ptr(), x=acts[name + ".block.2"].data_ptr(),
-                          scale=ones(4 * c).data_ptr(), out=dw1.data_ptr(), channels=c, height=h, width=w, out_channels=4 * c)
-                    grads[name + ".block.3.weight"] = dw1
-                keep.append(packed2)
+                    pb.wgrad(name + ".block.3", dh, acts[name + ".block.2"], c, 4 * c, h, w)
                 if not (below or want(dw.weight, dw.bias, norm.weight, norm.bias)):
                     continue
-                packed1 = self._packed_rows_dgrad(fc1)
-                keep.append(packed1)
                 dn = tmp("dn", (batch, h, w, c), act)
-                pb.op(name + ".block.3 (dgrad)", 0, dz=dh.data_ptr(), weight=packed1.data_ptr(), out=dn.data_ptr(), channels=c,
-                      height=h, width=w, out_channels=4 * c)
+                pb.dgrad(name + ".block.3", self._packed_rows_dgrad(fc1), dh, dn, c, 4 * c, h, w)
                 d = tmp("d", (batch, h, w, c), torch.float32)
-                layer_norm_bwd(name + ".block.2", norm, dn, acts[name + ".block.0"], d, c, h, w)
-                if want(dw.weight, dw.bias):
+                pb.layer_norm_bwd(name + ".block.2", norm, self._f32(norm, "weight", norm.weight), dz=dn,
+                                  x=acts[name + ".block.0"], out=d, channels=c, height=h, width=w)
+                if want(dw.weight, dw.bias):   # kind 5: the depthwise taps' and bias gradient
                     dtaps = new((49, c), torch.float32)
-                    dbd = new((c,), torch.float32) if want(dw.bias) else None
+                    dbd = pb.grad(name + ".block.0.bias", (c,), dw.bias)
                     pb.op(name + ".block.0 (wgrad)", 5, dz=d.data_ptr(), x=acts[name + ".in"].data_ptr(), out=dtaps.data_ptr(),
                           dbias=_hip.ptr(dbd), channels=c, height=h, width=w)
                     if want(dw.weight):
                         grads[name + ".block.0.weight"] = dtaps.t().reshape(c, 1, 7, 7)
-                    if dbd is not None:
-                        grads[name + ".block.0.bias"] = dbd
-                if below:
+                if below:   # kind 6: the depthwise backward-data, the residual's gradient added
                     taps, _ = self._taps(dw)
                     keep.append(taps)
-                    dx = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
-                    flip ^= 1
+                    dx = pb.next_dy((batch, h, w, c))
                     pb.op(name + ".block.0 (dgrad)", 6, dz=d.data_ptr(), weight=taps.data_ptr(), add=dy.data_ptr(),
                           out=dx.data_ptr(), channels=c, height=h, width=w)
                     dy = dx
@@ -498,40 +416,21 @@ class ConvNeXtBackbone(HipBackbone):
                 c, co = conv.weight.shape[1], conv.weight.shape[0]
                 ho, wo = h // 2, w // 2
                 dzc = tmp("dzc", (batch, ho, wo, co), act)
-                dbc = new((co,), torch.float32) if want(conv.bias) else None
-                pb.op(name + ".1 (rows)", 2, dz=dy.data_ptr(), out=dzc.data_ptr(), dbias=_hip.ptr(dbc), channels=co, height=ho,
-                      width=wo)
-                if dbc is not None:
-                    grads[name + ".1.bias"] = dbc
-                if want(conv.weight):
+                pb.rows(name + ".1", dy, None, dzc, pb.grad(name + ".1.bias", (co,), conv.bias), co, ho, wo)
+                if want(conv.weight):   # kind 8: the normalised rows as 2x2 patches, the weight as [out, (ky, kx, in)] rows
                     patches = tmp("patches", (batch, ho, wo, 4 * c), act)
                     pb.op(name + ".1 (patches)", 8, x=acts[name + ".0"].data_ptr(), out=patches.data_ptr(), channels=c, height=h,
                           width=w)
-                    dwp = new((co, 4 * c), torch.float32)
-                    pb.op(name + ".1 (wgrad)", 1, dz=dzc.data_ptr(), x=patches.data_ptr(), scale=ones(co).data_ptr(),
-                          out=dwp.data_ptr(), channels=4 * c, height=ho, width=wo, out_channels=co)
+                    dwp = pb.wgrad(name + ".1", dzc, patches, 4 * c, co, ho, wo)
                     grads[name + ".1.weight"] = dwp.view(co, 2, 2, c).permute(0, 3, 1, 2)
                 dy_next = None
                 if below or want(norm.weight, norm.bias):
-                    packed = self._packed_rows_dgrad(conv)
-                    keep.append(packed)
                     dpatch = tmp("dpatch", (batch, ho, wo, 4 * c), act)
-                    pb.op(name + ".1 (dgrad)", 0, dz=dzc.data_ptr(), weight=packed.data_ptr(), out=dpatch.data_ptr(),
-                          channels=4 * c, height=ho, width=wo, out_channels=co)
-                    dn = tmp("dn", (batch, h, w, c), act)
+                    pb.dgrad(name + ".1", self._packed_rows_dgrad(conv), dzc, dpatch, 4 * c, co, ho, wo)
+                    dn = tmp("dn", (batch, h, w, c), act)   # kind 9: the patches' gradient back on the pixels
                     pb.op(name + ".1 (pixels)", 9, dz=dpatch.data_ptr(), out=dn.data_ptr(), channels=c, height=h, width=w)
-                    dy_next = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
-                    flip ^= 1
-                    layer_norm_bwd(name + ".0", norm, dn, acts[name + ".in"], dy_next, c, h, w)
+                    dy_next = pb.next_dy((batch, h, w, c))
+                    pb.layer_norm_bwd(name + ".0", norm, self._f32(norm, "weight", norm.weight), dz=dn, x=acts[name + ".in"],
+                                      out=dy_next, channels=c, height=h, width=w)
                 dy = dy_next
         return pb.ops, pb.names, grads, keep
-
-    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
-                      ) -> Dict[str, Tensor]:
-        """Runs the backward plan on the stored activations; returns ``{parameter name: fp32 gradient}``."""
-        acts = state["acts"]
-        ops, _, grads, keep = self._backward_ops(acts, state["factors"], shape, cotangents, splits)
-        if ops:
-            dev = next(iter(acts.values())).device
-            self._run_plan(_hip.ConvnextBwdOpStruct, "sdetr_convnext_bwd", ops, dev)
-        return grads

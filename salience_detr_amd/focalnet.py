@@ -416,13 +416,7 @@ class FocalNetBackbone(HipBackbone):
         return pb.ops, outputs, keep, pb.names
 
     def forward_hip(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
-        if x.dtype != torch.float32:
-            x = x.float()
-        _hip.require_device("FocalNetBackbone", x=x)
-        for t in self.parameters():
-            _hip.require_device("FocalNetBackbone", parameter=t.detach())
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f"FocalNetBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
+        x = self._check_image(x)
         ops, outputs, keep, _ = self.build_plan(x, splits)
         self._run_plan(_hip.FocalnetOpStruct, "sdetr_focalnet", ops, x.device)
         return outputs

@@ -28,9 +28,10 @@ than 7 / 12 or a head dimension other than 32 run the composite too (``hip_form(
 form raises: the hot path has no CPU fallback.
 
 Training in HIP (``set_train_form("hip")``, ``csrc/swin_backward.hip``; the interface and its autograd node are
-``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored state and ``_run_backward``): a forward that
-needs autograd runs the same plan inside one autograd node.  Every block from the lowest trainable module on gets buffers
-of its own (the stream at its input and after the attention branch, both LayerNorm outputs, the qkv rows, the attention
+``backbone_base.HipBackbone``'s, as are ``_trainable``, ``_first_trainable``, the test hooks and ``_run_backward``; this
+module gives ``_sequence``, the stored state and ``_backward_ops``, its own kinds next to the emitters of the base's
+``BackwardPlanBuilder``): a forward that needs autograd runs the same plan inside one autograd node.  Every block from
+the lowest trainable module on gets buffers of its own (the stream at its input and after the attention branch, both LayerNorm outputs, the qkv rows, the attention
 rows, the values before the GELU and after it), fc1 also stores its pre-GELU values (``aux``) and proj / fc2 multiply by
 the branch's stochastic-depth factor per sample (``row_scale``; two draws per block, on the device, exactly as
 ``StochasticDepth`` draws them).  The backward is one ``sdetr_swin_bwd_run`` call over ``_backward_ops``: it stops below
@@ -47,7 +48,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import HipBackbone, Permute, PlanBuilder, StochasticDepth
+from .backbone_base import BackwardPlanBuilder, HipBackbone, Permute, PlanBuilder, StochasticDepth
 from .derived import derived
 
 MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/backbone_rows_core.h); the merging norm sees 4 C
@@ -353,15 +354,6 @@ class SwinBackbone(HipBackbone):
         def layer_norm(name, norm, src, out, h, w, c, out_f32=False):
             pb.layer_norm(name, 3, self._affine(norm), norm.eps, src, out, h, w, c, out_f32)
 
-        def draw(sd):   # StochasticDepth.forward's own draw, in its order
-            if train is None or not sd.training or sd.p == 0.0:
-                return None
-            factor = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=x.device).bernoulli_(1.0 - sd.p)
-            if sd.p < 1.0:
-                factor.div_(1.0 - sd.p)
-            keep.append(factor)
-            return factor
-
         stem = self.body.features[0]
         patch, c = stem[0].kernel_size[0], stem[0].out_channels
         h, w = x.shape[2] // patch, x.shape[3] // patch
@@ -390,7 +382,8 @@ class SwinBackbone(HipBackbone):
                     a1 = a2 = a_in
                     qkv_b, att_b, pre, mid_b = qkv, a_att, None, mid
                     x_in = x_mid = x_out = stream
-                f_attn, f_mlp = draw(blk.stochastic_depth), draw(blk.stochastic_depth)
+                sd = blk.stochastic_depth   # two draws per block: the attention branch first, then the MLP branch
+                f_attn, f_mlp = pb.draw(sd, batch, train is not None), pb.draw(sd, batch, train is not None)
                 if f_attn is not None:
                     factors[prefix + ".attn"], factors[prefix + ".mlp"] = f_attn.view(batch), f_mlp.view(batch)
                 layer_norm(prefix + ".norm1", blk.norm1, x_in, a1, h, w, c)
@@ -432,13 +425,7 @@ class SwinBackbone(HipBackbone):
     def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
         """``state`` (a dict): a training forward; it receives ``"first"``, ``"acts"`` and ``"factors"``, see
         ``build_plan``."""
-        if x.dtype != torch.float32:
-            x = x.float()
-        _hip.require_device("SwinBackbone", x=x)
-        for t in self.parameters():
-            _hip.require_device("SwinBackbone", parameter=t.detach())
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f"SwinBackbone: expected [B, 3, H, W], got {tuple(x.shape)}")
+        x = self._check_image(x)
         if not self.hip_form():
             raise RuntimeError("SwinBackbone: this configuration has no HIP form (window 7 / 12, head dimension 32)")
         if state is not None:
@@ -454,6 +441,7 @@ class SwinBackbone(HipBackbone):
                      "than 32, a width that is no multiple of 32, a norm other than nn.LayerNorm)",
                      "the stem (patch embedding and its LayerNorm, features.0) is trainable and has no HIP backward: freeze "
                      "it with freeze_indices")
+    backward_struct, backward_prefix = _hip.SwinBwdOpStruct, "sdetr_swin_bwd"
 
     def _stem_modules(self):
         return (self.body.features[0],)
@@ -478,29 +466,12 @@ class SwinBackbone(HipBackbone):
                 seq.append(("merge", f"0.features.{2 * i + 2}", merging))
         return seq
 
-    def _first_trainable(self) -> Optional[int]:
-        """The index in ``_sequence()`` of the lowest module with a trainable parameter: where the backward stops."""
-        for idx, (_, _, m) in enumerate(self._sequence()):
-            if any(p.requires_grad for p in m.parameters()):
-                return idx
-        return None
-
-    def _trainable(self) -> List[Tuple[str, nn.Parameter]]:
-        return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
-
-    def saved_activations(self) -> Dict[str, Tensor]:
-        """Test hook (read-only): what the last ``"hip"`` training forward stored, by name.  Of a block: ``<block>.in`` and
-        ``.mid`` (the fp32 stream at its input and after the attention branch), ``.norm1`` / ``.norm2`` (the LayerNorm
-        outputs), ``.attn.qkv`` (the qkv rows), ``.attn`` (the attention rows), ``.mlp.0`` (before the GELU), ``.mlp.1``
-        (after it); of a merging layer ``<merging>.in`` (the stream it reads) and ``.norm`` (the gathered LayerNorm rows).
-        Valid while that forward's autograd graph is alive."""
-        return dict(self._train_state()["acts"])
-
-    def stochastic_depth_factors(self) -> Dict[str, Tensor]:
-        """Test hook (read-only): ``{<block>.attn | <block>.mlp: factors [B]}`` (0 or 1 / (1 - p)) the last ``"hip"``
-        training forward drew, in forward order (the attention branch, then the MLP branch); blocks with ``p == 0`` or in
-        ``eval()`` draw nothing.  Valid as ``saved_activations``."""
-        return dict(self._train_state()["factors"])
+    # ``saved_activations()`` (HipBackbone's test hook) holds, by name, of a block: ``<block>.in`` and ``.mid`` (the fp32
+    # stream at its input and after the attention branch), ``.norm1`` / ``.norm2`` (the LayerNorm outputs), ``.attn.qkv``
+    # (the qkv rows), ``.attn`` (the attention rows), ``.mlp.0`` (before the GELU), ``.mlp.1`` (after it); of a merging
+    # layer ``<merging>.in`` (the stream it reads) and ``.norm`` (the gathered LayerNorm rows).
+    # ``stochastic_depth_factors()`` is ``{<block>.attn | <block>.mlp: factors [B]}``, in forward order (the attention
+    # branch, then the MLP branch).
 
     def _table_pairs(self, attn: ShiftedWindowAttention) -> Tuple[Tensor, Tensor]:
         """The (query, key) pairs of every table entry as a CSR list: ``(order int32 [N * N], offsets int32 [entries + 1])``."""
@@ -522,60 +493,8 @@ class SwinBackbone(HipBackbone):
         batch, _, height, width = shape
         seq, first = self._sequence(), self._first_trainable()
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
-        anchor = next(iter(acts.values()))
-        dev = anchor.device
-        pb = PlanBuilder(_hip.SwinBwdOpStruct, anchor, batch=batch, splits=splits)
-        new, keep = pb.new, pb.keep
-        scratch: Dict[tuple, Tensor] = {}
-        grads: Dict[str, Tensor] = {}
-
-        def tmp(tag, shape_, dtype):   # a buffer the next block may overwrite: the plan runs in order on one stream
-            key = (tag, tuple(shape_), dtype)
-            if key not in scratch:
-                scratch[key] = new(shape_, dtype)
-            return scratch[key]
-
-        def ones(n):
-            key = ("ones", n)
-            if key not in scratch:
-                scratch[key] = torch.ones(n, device=dev)
-                keep.append(scratch[key])
-            return scratch[key]
-
-        def want(*params):
-            return any(p is not None and p.requires_grad for p in params)
-
-        def linear_bwd(name, layer, dz, x, out, ci, co, h, w):   # dW = dz^T x; out (or None) = dz W
-            if want(layer.weight):
-                dw = new((co, ci), torch.float32)
-                pb.op(name + " (wgrad)", 1, dz=dz.data_ptr(), x=x.data_ptr(), scale=ones(co).data_ptr(), out=dw.data_ptr(),
-                      channels=ci, height=h, width=w, out_channels=co)
-                grads[name + ".weight"] = dw
-            if out is not None:
-                packed = self._packed_rows_dgrad(layer)
-                keep.append(packed)
-                pb.op(name + " (dgrad)", 0, dz=dz.data_ptr(), weight=packed.data_ptr(), out=out.data_ptr(), channels=ci, height=h,
-                      width=w, out_channels=co)
-
-        def rows(name, dy_, factor, out, bias, c, h, w):   # out = factor[n] * dy in the compute dtype, the bias gradient
-            db = new((c,), torch.float32) if want(bias) else None
-            pb.op(name + " (rows)", 2, dz=dy_.data_ptr(), scale=_hip.ptr(factor), out=out.data_ptr(), dbias=_hip.ptr(db), channels=c,
-                  height=h, width=w)
-            return db
-
-        def norm_grads(name, norm, kind, **fields):   # a LayerNorm backward (kind 4, or 8 over the merging gather)
-            gamma = self._f32(norm, "weight", norm.weight)
-            keep.append(gamma)
-            affine = want(norm.weight, norm.bias)
-            n = norm.weight.numel()
-            dgam = new((n,), torch.float32) if affine else None
-            dbet = new((n,), torch.float32) if affine else None
-            pb.op(name + (" (layer norm)" if kind == 4 else " (merging)"), kind, gamma=gamma.data_ptr(), dgamma=_hip.ptr(dgam),
-                  dbeta=_hip.ptr(dbet), eps=float(norm.eps), **fields)
-            if want(norm.weight):
-                grads[name + ".weight"] = dgam
-            if want(norm.bias):
-                grads[name + ".bias"] = dbet
+        pb = BackwardPlanBuilder(self.backward_struct, next(iter(acts.values())), batch=batch, splits=splits)
+        keep, tmp, want, grad = pb.keep, pb.tmp, pb.want, pb.grad
 
         # the size and width of every module's input
         patch = self.body.features[0][0].kernel_size[0]
@@ -587,17 +506,7 @@ class SwinBackbone(HipBackbone):
         last_of = {f"0.features.{2 * i + 1}.{len(blocks) - 1}": i for i, blocks, _ in self._stages()}
         merge_of = {f"0.features.{2 * i + 2}": i for i, _, merging in self._stages() if merging is not None}
 
-        def ingest(name, stage, dy_, c, h, w):   # the returned map's cotangent (+ what arrives from above) as fp32 rows
-            g = cotangents.get(f"features.{2 * stage + 1}")
-            if g is None and dy_ is not None:
-                return dy_
-            g = torch.zeros((batch, c, h, w), device=dev) if g is None else g.to(torch.float32).contiguous()
-            keep.append(g)
-            out = new((batch, h, w, c), torch.float32)
-            pb.op(name + " (ingest)", 5, dz=g.data_ptr(), add=_hip.ptr(dy_), out=out.data_ptr(), channels=c, height=h, width=w)
-            return out
-
-        dy, flip = None, 0
+        dy = None
         for idx in range(len(seq) - 1, (first if first is not None else len(seq)) - 1, -1):
             kind, name, m = seq[idx]
             h, w, c = sizes[idx]
@@ -606,76 +515,65 @@ class SwinBackbone(HipBackbone):
                 stage = merge_of[name]
                 ho, wo = (h + 1) // 2, (w + 1) // 2
                 dzr = tmp("dzr", (batch, ho, wo, 2 * c), act)
-                rows(name + ".reduction", dy, None, dzr, None, 2 * c, ho, wo)
+                pb.rows(name + ".reduction", dy, None, dzr, None, 2 * c, ho, wo)
                 dgath = tmp("dgath", (batch, ho, wo, 4 * c), act)
-                linear_bwd(name + ".reduction", m.reduction, dzr, acts[name + ".norm"], dgath, 4 * c, 2 * c, ho, wo)
-                add = ingest(name, stage, None, c, h, w) if stage in self.return_indices else None
-                dx = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
-                flip ^= 1
-                norm_grads(name + ".norm", m.norm, 8, dz=dgath.data_ptr(), x=acts[name + ".in"].data_ptr(), add=_hip.ptr(add),
-                           out=dx.data_ptr(), channels=c, height=h, width=w)
-                dy = dx
+                if want(m.reduction.weight):
+                    pb.wgrad(name + ".reduction", dzr, acts[name + ".norm"], 4 * c, 2 * c, ho, wo)
+                pb.dgrad(name + ".reduction", self._packed_rows_dgrad(m.reduction), dzr, dgath, 4 * c, 2 * c, ho, wo)
+                add = None
+                if stage in self.return_indices:   # kind 5: the NCHW ingest
+                    add = pb.ingest(name, 5, cotangents.get(f"features.{2 * stage + 1}"), None, c, h, w)
+                dy = pb.next_dy((batch, h, w, c))   # kind 8: the LayerNorm backward scattered back over the 2 x 2 gather
+                pb.layer_norm_bwd(name + ".norm", m.norm, self._f32(m.norm, "weight", m.norm.weight), 8, " (merging)", dz=dgath,
+                                  x=acts[name + ".in"], add=add, out=dy, channels=c, height=h, width=w)
                 continue
             stage = last_of.get(name)
             if stage is not None and stage in self.return_indices and f"0.features.{2 * stage + 2}" not in merge_of:
-                dy = ingest(name, stage, dy, c, h, w)
+                dy = pb.ingest(name, 5, cotangents.get(f"features.{2 * stage + 1}"), dy, c, h, w)
             at, fc1, fc2 = m.attn, m.mlp[0], m.mlp[3]
             hidden = fc1.out_features
             # the MLP branch
             dzs = tmp("dzs", (batch, h, w, c), act)
-            db = rows(name + ".mlp.3", dy, factors.get(name + ".mlp"), dzs, fc2.bias, c, h, w)
-            if db is not None:
-                grads[name + ".mlp.3.bias"] = db
+            pb.rows(name + ".mlp.3", dy, factors.get(name + ".mlp"), dzs, grad(name + ".mlp.3.bias", (c,), fc2.bias), c, h, w)
             dh = tmp("dh", (batch, h, w, hidden), act)
-            linear_bwd(name + ".mlp.3", fc2, dzs, acts[name + ".mlp.1"], dh, hidden, c, h, w)
-            db1 = new((hidden,), torch.float32) if want(fc1.bias) else None
-            pb.op(name + ".mlp.1 (gelu)", 3, dz=dh.data_ptr(), x=acts[name + ".mlp.0"].data_ptr(), out=dh.data_ptr(),
-                  dbias=_hip.ptr(db1), channels=hidden, height=h, width=w)
-            if db1 is not None:
-                grads[name + ".mlp.0.bias"] = db1
+            if want(fc2.weight):
+                pb.wgrad(name + ".mlp.3", dzs, acts[name + ".mlp.1"], hidden, c, h, w)
+            pb.dgrad(name + ".mlp.3", self._packed_rows_dgrad(fc2), dzs, dh, hidden, c, h, w)
+            pb.gelu(name + ".mlp.1", dh, acts[name + ".mlp.0"], grad(name + ".mlp.0.bias", (hidden,), fc1.bias), hidden, h, w)
             dn = tmp("dn", (batch, h, w, c), act)
-            linear_bwd(name + ".mlp.0", fc1, dh, acts[name + ".norm2"], dn, c, hidden, h, w)
+            if want(fc1.weight):
+                pb.wgrad(name + ".mlp.0", dh, acts[name + ".norm2"], c, hidden, h, w)
+            pb.dgrad(name + ".mlp.0", self._packed_rows_dgrad(fc1), dh, dn, c, hidden, h, w)
             dmid = tmp("dmid", (batch, h, w, c), torch.float32)
-            norm_grads(name + ".norm2", m.norm2, 4, dz=dn.data_ptr(), x=acts[name + ".mid"].data_ptr(), add=dy.data_ptr(),
-                       out=dmid.data_ptr(), channels=c, height=h, width=w)
+            pb.layer_norm_bwd(name + ".norm2", m.norm2, self._f32(m.norm2, "weight", m.norm2.weight), dz=dn, x=acts[name + ".mid"],
+                              add=dy, out=dmid, channels=c, height=h, width=w)
             # the attention branch
-            db = rows(name + ".attn.proj", dmid, factors.get(name + ".attn"), dzs, at.proj.bias, c, h, w)
-            if db is not None:
-                grads[name + ".attn.proj.bias"] = db
+            pb.rows(name + ".attn.proj", dmid, factors.get(name + ".attn"), dzs, grad(name + ".attn.proj.bias", (c,), at.proj.bias),
+                    c, h, w)
             datt = tmp("datt", (batch, h, w, c), act)
-            linear_bwd(name + ".attn.proj", at.proj, dzs, acts[name + ".attn"], datt, c, c, h, w)
+            if want(at.proj.weight):
+                pb.wgrad(name + ".attn.proj", dzs, acts[name + ".attn"], c, c, h, w)
+            pb.dgrad(name + ".attn.proj", self._packed_rows_dgrad(at.proj), dzs, datt, c, c, h, w)
             table, qkv_bias = self._attention_operands(at)
             order, offsets = self._table_pairs(at)
             keep.extend((table, qkv_bias, order, offsets))
             dqkv, dpad = tmp("dqkv", (batch, h, w, 3 * c), act), tmp("dpad", (3 * c,), torch.float32)
-            dtable = new(tuple(at.relative_position_bias_table.shape), torch.float32) if want(at.relative_position_bias_table) else None
+            dtable = grad(name + ".attn.relative_position_bias_table", tuple(at.relative_position_bias_table.shape),
+                          at.relative_position_bias_table)
             pb.op(name + ".attn (attention)", 6, x=acts[name + ".attn.qkv"].data_ptr(), dz=datt.data_ptr(), bias=qkv_bias.data_ptr(),
                   table=table.data_ptr(), order=order.data_ptr(), offsets=offsets.data_ptr(), out=dqkv.data_ptr(),
                   dbias=dpad.data_ptr(), dtable=_hip.ptr(dtable), channels=c, height=h, width=w, window=at.window_size[0],
                   shift=at.shift_size[0], heads=at.num_heads)
-            if dtable is not None:
-                grads[name + ".attn.relative_position_bias_table"] = dtable
-            if want(at.qkv.bias):
-                dbq = new((3 * c,), torch.float32)
+            dbq = grad(name + ".attn.qkv.bias", (3 * c,), at.qkv.bias)
+            if dbq is not None:   # kind 7: the column sums of dqkv plus the padding tokens' share
                 pb.op(name + ".attn.qkv (bias)", 7, dz=dqkv.data_ptr(), add=dpad.data_ptr(), dbias=dbq.data_ptr(), channels=3 * c,
                       height=h, width=w)
-                grads[name + ".attn.qkv.bias"] = dbq
-            linear_bwd(name + ".attn.qkv", at.qkv, dqkv, acts[name + ".norm1"], dn, c, 3 * c, h, w)
+            if want(at.qkv.weight):
+                pb.wgrad(name + ".attn.qkv", dqkv, acts[name + ".norm1"], c, 3 * c, h, w)
+            pb.dgrad(name + ".attn.qkv", self._packed_rows_dgrad(at.qkv), dqkv, dn, c, 3 * c, h, w)
             # (the lowest block still needs norm1's dgamma / dbeta; its input gradient lands in a buffer nobody reads)
-            dx = tmp(f"dy{flip}", (batch, h, w, c), torch.float32)
-            flip ^= 1
-            norm_grads(name + ".norm1", m.norm1, 4, dz=dn.data_ptr(), x=acts[name + ".in"].data_ptr(), add=dmid.data_ptr(),
-                       out=dx.data_ptr(), channels=c, height=h, width=w)
+            dx = pb.next_dy((batch, h, w, c))
+            pb.layer_norm_bwd(name + ".norm1", m.norm1, self._f32(m.norm1, "weight", m.norm1.weight), dz=dn, x=acts[name + ".in"],
+                              add=dmid, out=dx, channels=c, height=h, width=w)
             dy = dx if below else None
-        return pb.ops, pb.names, grads, keep
-
-    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
-                      ) -> Dict[str, Tensor]:
-        """Runs the backward plan on the stored activations; returns ``{parameter name: fp32 gradient}``."""
-        acts = state["acts"]
-        if not acts:
-            return {}
-        ops, _, grads, keep = self._backward_ops(acts, state["factors"], shape, cotangents, splits)
-        if ops:
-            self._run_plan(_hip.SwinBwdOpStruct, "sdetr_swin_bwd", ops, next(iter(acts.values())).device)
-        return grads
+        return pb.ops, pb.names, pb.grads, keep
