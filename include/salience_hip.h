@@ -1201,6 +1201,81 @@ int sdetr_frontend_conv(sdetr_stream_t stream, const sdetr_frontend_level *level
 int sdetr_frontend_groupnorm(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
                              int out_channels, int num_groups, float eps, const void *workspace, int64_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training the ChannelMapper (csrc/frontend.hip: the training forward's GroupNorm; csrc/frontend_backward.hip: the backward).
+ *
+ * sdetr_frontend_groupnorm_train: sdetr_frontend_groupnorm's launch -- the same kernel, the same arithmetic, the same fixed
+ * merge order: out is bit-identical -- that also keeps what the backward reads.  z / stats: host arrays of n_levels device
+ * pointers; z[l] f32 NCHW [batch, out_channels, Ho, Wo] receives the raw convolution of level l (for a 3x3 level the sum of
+ * the split-K partials; it must not alias out), stats[l] f32 [batch][num_groups][2] the group's (mean, rstd).
+ *
+ * sdetr_frontend_bwd_op, by kind.  Activation gradients between ops are channels-last in the compute dtype (f32 with
+ * precision 0, the library's 16-bit type with precision 1), the operands sdetr_backbone_dgrad / _wgrad read.  A level is a
+ * bias-free conv, kernel_size 1 (stride 1) or 3 (stride 2, padding 1), from in_channels at height x width to out_channels
+ * at Ho x Wo (kernel 1: height x width; kernel 3: (height - 1) / 2 + 1).
+ *   0 dgrad:   dz [batch, Ho, Wo, out_channels], weight = sdetr_backbone_pack_dgrad's planes of the conv weight, add (or
+ *              NULL) a gradient shaped as out; out [batch, height, width, in_channels] = conv backward-data (+ add).
+ *              sdetr_backbone_dgrad's kernel.  in_channels % 32 == 0, out_channels % 8 == 0.
+ *   1 wgrad:   dz as above, x = the level's input [batch, height, width, in_channels] (compute dtype), scale f32
+ *              [out_channels] (ones); out f32 [out_channels, in_channels, k, k].  sdetr_backbone_wgrad's kernel.
+ *   2 rows:    x f32 NCHW [batch, in_channels, height, width] -> out channels-last [batch, height, width, in_channels] in
+ *              the compute dtype (the wgrad operand).  Kind 2 of sdetr_backbone_bwd_op, through sdetr_backbone_bwd_run.
+ *   3 GroupNorm backward at a map of height x width (the level's OUTPUT size) with out_channels channels in `groups`
+ *              groups: dz = dy f32 NCHW [batch, out_channels, height, width], the cotangent of the level's output; add (or
+ *              NULL) channels-last [batch, height, width, out_channels] in the compute dtype, a gradient of the same
+ *              output from a later level that read it; z and stats as sdetr_frontend_groupnorm_train wrote them; gamma f32
+ *              [out_channels].  With xh = (z - mean) * rstd and g = gamma * (dy + add):
+ *              out [batch, height, width, out_channels] channels-last, compute dtype = rstd * (g - mean_group(g) -
+ *              xh * mean_group(g * xh)), the means over the group's (out_channels / groups) * height * width elements;
+ *              dgamma f32 [out_channels] = sum over batch and pixels of (dy + add) * xh, dbeta = that sum of (dy + add):
+ *              both pointers or neither.  xh always comes from z and stats, never from the output (gamma may be zero).
+ *              Two passes: per-(image, channel) sums over 128-pixel tiles into the workspace, merged in tile order, then in
+ *              image order (dgamma, dbeta) and channel order (the group means); then the element-wise pass, which turns
+ *              NCHW into channels-last through LDS.  Any out_channels % groups == 0.  eps is GroupNorm's (stats already
+ *              hold rstd: it is checked, not read).
+ *   4 egest:   dz channels-last [batch, height, width, in_channels] in the compute dtype, add (or NULL) a second such
+ *              tensor -> out f32 NCHW [batch, in_channels, height, width] = dz (+ add), summed in f32: the gradient handed
+ *              back to a backbone map.
+ * splits: 0 = automatic, n > 0 = n pieces of the reduction of a dgrad / wgrad (as in sdetr_backbone_bwd_op); no other kind
+ * reads it.  No atomics: every sum has a fixed order through the workspace; every launch writes every element of its
+ * outputs; nothing syncs with the host.  Every tensor 16-byte aligned.  sdetr_frontend_bwd_workspace_bytes: the largest
+ * need of a plan (-1: a bad op).  sdetr_frontend_bwd_op_run runs one op; sdetr_frontend_bwd_run a whole plan in order,
+ * validated before the first launch (a bad op: SDETR_EINVAL and a message in sdetr_last_error, nothing launched).
+ * --------------------------------------------------------------------------------------------- */
+int sdetr_frontend_groupnorm_train(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
+                                   int out_channels, int num_groups, float eps, const void *workspace,
+                                   int64_t workspace_bytes, float *const *z, float *const *stats);
+
+typedef struct sdetr_frontend_bwd_op {
+    int kind;
+    const void *dz;
+    const void *x;
+    const void *weight;
+    const float *scale;
+    const void *add;
+    const float *z;
+    const float *stats;
+    const float *gamma;
+    void *out;
+    float *dgamma;
+    float *dbeta;
+    int batch;
+    int in_channels;
+    int height;
+    int width;
+    int out_channels;
+    int kernel_size;
+    int groups;
+    int splits;
+    float eps;
+} sdetr_frontend_bwd_op;
+
+int64_t sdetr_frontend_bwd_workspace_bytes(const sdetr_frontend_bwd_op *ops, int n_ops, int precision);
+int sdetr_frontend_bwd_op_run(sdetr_stream_t stream, const sdetr_frontend_bwd_op *op, int precision, void *workspace,
+                              int64_t workspace_bytes);
+int sdetr_frontend_bwd_run(sdetr_stream_t stream, const sdetr_frontend_bwd_op *ops, int n_ops, int precision,
+                           void *workspace, int64_t workspace_bytes);
+
 /* sdetr_frontend_masks_positions: ONE launch for all levels.  mask u8 (bool) [batch, height, width], nonzero on padding.
  * level_hw: host int array [n_levels][2] = (H_l, W_l).  Per level: level_masks[l] u8 [batch, H_l, W_l] = torch's nearest
  * down-sample (source pixel min(int(floorf(dst * ((float)in / out))), in - 1)); level_pos[l] f32 [batch, 2F, H_l, W_l]

@@ -17,10 +17,22 @@ How it runs (inference: grad disabled, or nothing that requires grad):
 The HIP path serves the form every reference config uses: ``kernel_size=1, stride=1, groups=1, dilation=1``,
 ``GroupNorm`` with ``out_channels % num_groups == 0``, no activation, no conv bias, every input width a multiple of 32
 (``out_channels`` too when a second extra level reads it), on HIP tensors, parameters of any float dtype (the kernels
-read fp32 / packed copies of them).  Anything else, and every call with grad enabled on something that requires grad (training), takes
-the differentiable plain-torch composite on the device (``F.conv2d`` + ``F.group_norm``): it is the autograd path of this
-row (there is no HIP backward of the mapper).  A CPU tensor on the HIP form raises: the hot path has no CPU fallback.
+read fp32 / packed copies of them).  Anything else, and by default every call with grad enabled on something that requires
+grad (training), takes the differentiable plain-torch composite on the device (``F.conv2d`` + ``F.group_norm``), the default
+autograd path of this row.  A CPU tensor on the HIP form raises: the hot path has no CPU fallback.
+
+Training in HIP (``set_train_form("hip")``, ``csrc/frontend_backward.hip``; the interface is the backbones'): a forward that
+needs autograd runs the same convolution launches and ``sdetr_frontend_groupnorm_train`` -- the inference GroupNorm, bit for
+bit, which also keeps the raw convolution ``z`` and every group's (mean, rstd) -- inside ONE autograd node over the backbone
+maps and the trainable parameters.  Its backward is one ``sdetr_frontend_bwd_run`` plan (``build_backward_plan``), levels
+from the last to the first: the GroupNorm backward (from ``z`` and the statistics, never from the output: gamma may be
+zero), the backbone's backward-weight and backward-data kernels on its channels-last result, and one egest per input that
+requires grad, back to fp32 NCHW.  Stored: ``z``, the statistics and the inputs themselves (no copy).  Served:
+``hip_form()``, ``out_channels % 8 == 0``, float32 or bfloat16, HIP tensors; anything else raises at forward with the reason
+(``hip_train_reason``), it never falls back.
 """
+import ctypes
+import weakref
 from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -28,6 +40,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _hip
+from .backbone_base import BackwardPlanBuilder, _TrainState
 from .derived import derived
 
 
@@ -116,6 +129,8 @@ class ChannelMapper(nn.Module):
     def forward(self, inputs: Union[Dict[str, Tensor], Sequence[Tensor]]) -> List[Tensor]:
         inputs = list(inputs.values()) if isinstance(inputs, dict) else list(inputs)
         assert len(inputs) == len(self.in_channels)
+        if self.train_form == "hip" and self._needs_autograd(inputs):
+            return self.forward_hip_train(inputs)
         if self._needs_autograd(inputs) or not self.hip_form():
             return self.forward_torch(inputs)
         return self.forward_hip(inputs)
@@ -162,7 +177,9 @@ class ChannelMapper(nn.Module):
                                         x.shape[3], self.convs[i][0].kernel_size[0], out.data_ptr(), gamma.data_ptr(),
                                         beta.data_ptr())
 
-    def _run(self, levels: List["_hip.FrontendLevelStruct"], batch: int, device) -> None:
+    def _run(self, levels: List["_hip.FrontendLevelStruct"], batch: int, device, kept: Sequence[Tensor] = ()) -> None:
+        """One convolution launch and one GroupNorm launch over ``levels``; ``kept`` (``z`` and ``stats`` of every level,
+        in level order) makes it the training forward's GroupNorm."""
         n = len(levels)
         arr = (_hip.FrontendLevelStruct * n)(*levels)
         gn = self.convs[0][1]
@@ -174,10 +191,16 @@ class ChannelMapper(nn.Module):
         precision = self._precision()
         _hip.launch("sdetr_frontend_conv", lib, device, arr, n, batch, self.out_channels, precision, ws.data_ptr(),
                     ws_bytes, what="ChannelMapper (conv)")
-        _hip.launch("sdetr_frontend_groupnorm", lib, device, arr, n, batch, self.out_channels, gn.num_groups,
-                    gn.eps, ws.data_ptr(), ws_bytes, what="ChannelMapper (groupnorm)")
+        if kept:
+            z = (ctypes.c_void_p * n)(*[t.data_ptr() for t in kept[0::2]])
+            stats = (ctypes.c_void_p * n)(*[t.data_ptr() for t in kept[1::2]])
+            _hip.launch("sdetr_frontend_groupnorm_train", lib, device, arr, n, batch, self.out_channels, gn.num_groups,
+                        gn.eps, ws.data_ptr(), ws_bytes, z, stats, what="ChannelMapper (groupnorm, training)")
+        else:
+            _hip.launch("sdetr_frontend_groupnorm", lib, device, arr, n, batch, self.out_channels, gn.num_groups,
+                        gn.eps, ws.data_ptr(), ws_bytes, what="ChannelMapper (groupnorm)")
 
-    def forward_hip(self, inputs: Sequence[Tensor]) -> List[Tensor]:
+    def _check_inputs(self, inputs: Sequence[Tensor]) -> List[Tensor]:
         xs = []
         for x in inputs:
             if x.dtype != torch.float32:
@@ -186,24 +209,230 @@ class ChannelMapper(nn.Module):
             xs.append(x)
         for p in self.parameters():
             _hip.require_device("ChannelMapper", parameter=p.detach())
-        batch, dev = xs[0].shape[0], xs[0].device
-        if any(x.shape[0] != batch for x in xs):
+        if any(x.shape[0] != xs[0].shape[0] for x in xs):
             raise RuntimeError("ChannelMapper: inputs of different batch sizes")
         for x, c in zip(xs, self.in_channels):
             if x.dim() != 4 or x.shape[1] != c:
                 raise RuntimeError(f"ChannelMapper: expected [B, {c}, H, W], got {tuple(x.shape)}")
-        co, nin = self.out_channels, len(xs)
-        outs = [torch.empty(batch, co, x.shape[2], x.shape[3], device=dev, dtype=torch.float32) for x in xs]
-        levels = [self._level(i, x, o) for i, (x, o) in enumerate(zip(xs, outs))]
-        src = xs[-1]
-        for i in range(nin, len(self.convs)):
-            h, w = (src.shape[2] - 1) // 2 + 1, (src.shape[3] - 1) // 2 + 1
+        return xs
+
+    def build_plan(self, xs: Sequence[Tensor], state: Optional[dict] = None):
+        """The forward over the checked fp32 inputs ``xs`` as host data: ``(calls, outs, keep)``.  A call is ``(levels,
+        kept)``: the levels of one convolution + GroupNorm launch pair (a further extra level reads the previous
+        NORMALISED level: a call of its own) and, with ``state`` (the training forward), their ``z`` / ``stats`` buffers in
+        level order; ``state["acts"]`` receives what the backward reads, by name: ``input.<i>`` (the inputs themselves, no
+        copy), ``convs.<i>.z``, ``convs.<i>.stats`` and, of an extra level that a further one reads, ``convs.<i>.out`` (the
+        normalised map, the next level's input)."""
+        batch, dev, co, nin = xs[0].shape[0], xs[0].device, self.out_channels, len(xs)
+        groups = self.convs[0][1].num_groups
+        acts = None if state is None else state.setdefault("acts", {})
+        outs: List[Tensor] = []
+        calls: List[Tuple[list, List[Tensor]]] = [([], [])]
+        keep: List[Tensor] = list(xs)
+        for i in range(len(self.convs)):
+            src = xs[i] if i < nin else (xs[-1] if i == nin else outs[-1])
+            h, w = (src.shape[2], src.shape[3]) if i < nin else ((src.shape[2] - 1) // 2 + 1, (src.shape[3] - 1) // 2 + 1)
             out = torch.empty(batch, co, h, w, device=dev, dtype=torch.float32)
-            levels.append(self._level(i, src, out))
+            if i > nin:
+                calls.append(([], []))
+            calls[-1][0].append(self._level(i, src, out))
+            keep.extend((out, self._packed_weight(i)) + self._affine(i))
+            if acts is not None:
+                z = torch.empty_like(out)
+                stats = torch.empty(batch, groups, 2, device=dev, dtype=torch.float32)
+                calls[-1][1].extend((z, stats))
+                keep.extend((z, stats))
+                acts[f"convs.{i}.z"], acts[f"convs.{i}.stats"] = z, stats
+                if i < nin:
+                    acts[f"input.{i}"] = src
+                elif i < len(self.convs) - 1:
+                    # (an alias without autograd history: the returned map itself would tie the autograd node, which
+                    # owns this state, into a reference cycle with its own output)
+                    acts[f"convs.{i}.out"] = out.detach()
             outs.append(out)
-            if i > nin:   # reads the previous extra level after its GroupNorm: a call of its own
-                self._run(levels[:-1], batch, dev)
-                levels = levels[-1:]
-            src = out
-        self._run(levels, batch, dev)
+        return calls, outs, keep
+
+    def forward_hip(self, inputs: Sequence[Tensor], state: Optional[dict] = None) -> List[Tensor]:
+        xs = self._check_inputs(inputs)
+        calls, outs, _ = self.build_plan(xs, state)
+        for levels, kept in calls:
+            self._run(levels, xs[0].shape[0], xs[0].device, kept)
         return outs
+
+    # ------------------------------------------------------------------------------------------ training in HIP
+    train_form = "torch"
+
+    def set_train_form(self, form: str):
+        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
+        (the HIP forward inside one autograd node whose backward is one ``sdetr_frontend_bwd_run`` plan, see
+        ``forward_hip_train``).  ``"hip"`` on a module or inputs that are not eligible (``hip_train_reason``) raises at
+        forward: it never falls back."""
+        if form not in ("torch", "hip"):
+            raise ValueError(f"ChannelMapper.set_train_form: {form!r} is not 'torch' / 'hip'")
+        self.train_form = form
+        return self
+
+    def hip_train_reason(self, inputs: Optional[Sequence[Tensor]] = None) -> Optional[str]:
+        """Why the ``"hip"`` training form cannot serve this module (and ``inputs``); ``None`` when it can."""
+        if not self.hip_form():
+            return ("the configuration is not one the HIP kernels serve (a 1x1 stride-1 ungrouped bias-free conv + affine "
+                    "GroupNorm per level, every input width a multiple of 32)")
+        if self.out_channels % 8:
+            return f"out_channels {self.out_channels} is not a multiple of 8 (the backward-data and backward-weight kernels)"
+        if self.compute_dtype not in (torch.float32, torch.bfloat16):
+            return f"compute dtype {self.compute_dtype} is not float32 / bfloat16 (float16 has no loss scaling here)"
+        if inputs is not None and any(not x.is_cuda for x in inputs):
+            return "an input is a CPU tensor: the hot path has no CPU fallback"
+        return None
+
+    def hip_train_form(self, inputs: Optional[Sequence[Tensor]] = None) -> bool:
+        """True when ``set_train_form("hip")`` can train this module (on ``inputs``)."""
+        return self.hip_train_reason(inputs) is None
+
+    def forward_hip_train(self, inputs: Sequence[Tensor], splits: int = 0) -> List[Tensor]:
+        """The ``"hip"`` training form: ``forward_hip`` with the training GroupNorm as one autograd node over the inputs
+        and the trainable parameters.  The node keeps the raw convolutions ``z``, the (mean, rstd) of every group and the
+        inputs (no copy); its backward is one plan and returns fp32 gradients, which autograd accumulates."""
+        inputs = list(inputs.values()) if isinstance(inputs, dict) else list(inputs)
+        reason = self.hip_train_reason(inputs)
+        if reason is not None:
+            raise RuntimeError(f"ChannelMapper: the 'hip' training form cannot run: {reason}")
+        named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+        return list(_MapperTrainFunction.apply(self, len(inputs), splits, tuple(n for n, _ in named), *inputs,
+                                               *[p for _, p in named]))
+
+    def saved_activations(self) -> Dict[str, Tensor]:
+        """Test hook (read-only): what the last ``"hip"`` training forward stored, by the names of ``build_plan``.  Valid
+        while that forward's autograd graph is alive."""
+        state = self.__dict__.get("_train_state_ref")
+        state = state() if state is not None else None
+        if state is None:
+            raise RuntimeError("ChannelMapper: no 'hip' training forward is alive")
+        return dict(state["acts"])
+
+    def _packed_dgrad(self, i: int) -> Tensor:
+        """The backward-data planes of level ``i``'s conv weight (``sdetr_backbone_pack_dgrad`` with a unit scale), built
+        once per parameter version and precision."""
+        conv = self.convs[i][0]
+        w = conv.weight
+        precision, lib = self._precision(), self._lib()
+
+        def build():
+            co, ci, k = w.shape[0], w.shape[1], w.shape[2]
+            w32 = w.detach().to(torch.float32).contiguous()
+            ones = torch.ones(co, device=w.device)
+            packed = torch.empty(lib.sdetr_backbone_dgrad_packed_bytes(co, ci, k, precision) // 2, dtype=torch.int16,
+                                 device=w.device)
+            unused = torch.empty(co, dtype=torch.float32, device=w.device)
+            _hip.launch("sdetr_backbone_pack_dgrad", lib, w.device, w32.data_ptr(), ones.data_ptr(), ones.data_ptr(), 0.0, co,
+                        ci, k, precision, packed.data_ptr(), unused.data_ptr(), what="ChannelMapper (pack dgrad)")
+            return packed
+        return derived(conv, "frontend_packed_dgrad", (w,), build, extra=(precision, self.compute_dtype))
+
+    def build_backward_plan(self, acts: Dict[str, Tensor], cotangents: Sequence[Optional[Tensor]],
+                            input_grads: Sequence[bool], splits: int = 0):
+        """The backward of one training forward as ``sdetr_frontend_bwd_op`` ops (kinds: 0 dgrad, 1 wgrad, 2 rows, 3
+        GroupNorm backward, 4 egest): ``(ops, names, grads, input_grads, keep)``.  Levels run from the last to the first,
+        so that an extra level's backward-data result reaches the level below (``add``) before that level's GroupNorm
+        backward.  Per level: the GroupNorm backward; for a trainable conv weight the input as channels-last rows (once per
+        input: the last backbone map feeds two levels) and the backward-weight; the backward-data where something below
+        wants a gradient.  An input that requires grad gets one egest, which adds its two backward-data results where it
+        has two.  ``grads``: ``{parameter name: fp32 tensor}``; ``input_grads``: fp32 NCHW tensors, ``None`` where not asked."""
+        nin, n_levels = len(self.in_channels), len(self.convs)
+        xs = [acts[f"input.{i}"] for i in range(nin)]
+        batch, co, act = xs[0].shape[0], self.out_channels, self.compute_dtype
+        b = BackwardPlanBuilder(_hip.FrontendBwdOpStruct, xs[0], batch=batch, splits=splits)
+        b.keep.extend(xs[1:])
+        rows: Dict[int, Tensor] = {}                    # the channels-last copy of a level's input, by level of the source
+        parts: List[List[Tensor]] = [[] for _ in xs]    # the backward-data results an input's gradient is the sum of
+        add: Optional[Tensor] = None                    # what the level above hands to this level's normalised output
+        trainable_below = [any(p.requires_grad for blk in self.convs[nin:i] for p in blk.parameters()) or input_grads[-1]
+                           for i in range(n_levels)]
+        for i in reversed(range(n_levels)):
+            conv, gn = self.convs[i]
+            name, k = f"convs.{i}", conv.kernel_size[0]
+            src = xs[i] if i < nin else (xs[-1] if i == nin else acts[f"convs.{i - 1}.out"])
+            src_key = min(i, nin - 1) if i <= nin else -i
+            ci, h, w = src.shape[1], src.shape[2], src.shape[3]
+            z, stats = acts[name + ".z"], acts[name + ".stats"]
+            ho, wo = z.shape[2], z.shape[3]
+            want_dx = trainable_below[i] if i > nin else input_grads[min(i, nin - 1)]
+            above, add = add, None
+            if not (want_dx or b.want(conv.weight, gn.weight, gn.bias)):
+                continue
+            cot = cotangents[i]
+            cot = torch.zeros_like(z) if cot is None else cot.to(torch.float32).contiguous()
+            gamma = self._affine(i)[0]
+            b.keep.extend((cot, z, stats, gamma, src))
+            affine = b.want(gn.weight, gn.bias)
+            dgamma = b.new((co,), torch.float32) if affine else None
+            dbeta = b.new((co,), torch.float32) if affine else None
+            dz = b.new((batch, ho, wo, co), act)
+            b.op(name + " (group norm)", 3, dz=cot.data_ptr(), add=_hip.ptr(above), z=z.data_ptr(), stats=stats.data_ptr(),
+                 gamma=gamma.data_ptr(), out=dz.data_ptr(), dgamma=_hip.ptr(dgamma), dbeta=_hip.ptr(dbeta), height=ho, width=wo,
+                 out_channels=co, groups=gn.num_groups, eps=float(gn.eps))
+            if b.want(gn.weight):
+                b.grads[name + ".1.weight"] = dgamma
+            if b.want(gn.bias):
+                b.grads[name + ".1.bias"] = dbeta
+            shape = dict(in_channels=ci, height=h, width=w, out_channels=co, kernel_size=k)
+            if b.want(conv.weight):
+                if src_key not in rows:
+                    rows[src_key] = b.new((batch, h, w, ci), act)
+                    b.op(name + " (rows)", 2, x=src.data_ptr(), out=rows[src_key].data_ptr(), in_channels=ci, height=h, width=w)
+                dw = b.grad(name + ".0.weight", tuple(conv.weight.shape), conv.weight)
+                b.op(name + " (wgrad)", 1, dz=dz.data_ptr(), x=rows[src_key].data_ptr(), scale=b.ones(co).data_ptr(),
+                     out=dw.data_ptr(), **shape)
+            if want_dx:
+                packed = self._packed_dgrad(i)
+                b.keep.append(packed)
+                dx = b.new((batch, h, w, ci), act)
+                b.op(name + " (dgrad)", 0, dz=dz.data_ptr(), weight=packed.data_ptr(), out=dx.data_ptr(), **shape)
+                if i > nin:
+                    add = dx
+                else:
+                    parts[min(i, nin - 1)].append(dx)
+        dxs: List[Optional[Tensor]] = []
+        for j, x in enumerate(xs):
+            if not parts[j]:
+                dxs.append(None)
+                continue
+            dxs.append(b.new(tuple(x.shape), torch.float32))
+            b.op(f"input.{j} (egest)", 4, dz=parts[j][0].data_ptr(), add=_hip.ptr(parts[j][1] if len(parts[j]) > 1 else None),
+                 out=dxs[-1].data_ptr(), in_channels=x.shape[1], height=x.shape[2], width=x.shape[3])
+        return b.ops, b.names, b.grads, dxs, b.keep
+
+    def _run_backward(self, state: dict, cotangents: Sequence[Optional[Tensor]], input_grads: Sequence[bool], splits: int = 0):
+        """Runs the backward plan on what the forward stored: ``({parameter name: fp32 gradient}, input gradients)``."""
+        ops, _, grads, dxs, keep = self.build_backward_plan(state["acts"], cotangents, input_grads, splits)
+        if ops:
+            lib, precision = self._lib(), self._precision()
+            arr = (_hip.FrontendBwdOpStruct * len(ops))(*ops)
+            ws_bytes = lib.sdetr_frontend_bwd_workspace_bytes(arr, len(ops), precision)
+            if ws_bytes < 0:
+                _hip.check(-1, "ChannelMapper (backward workspace)", lib)
+            dev = keep[0].device
+            ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
+            _hip.launch("sdetr_frontend_bwd_run", lib, dev, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
+                        what="ChannelMapper (backward)")
+        return grads, dxs
+
+
+class _MapperTrainFunction(torch.autograd.Function):
+    """``ChannelMapper.forward_hip_train``: inputs are the backbone maps and the trainable parameters, outputs the
+    levels' fp32 NCHW maps."""
+
+    @staticmethod
+    def forward(ctx, mapper: ChannelMapper, n_inputs: int, splits: int, names: Tuple[str, ...], *tensors: Tensor):
+        state = _TrainState()
+        outs = mapper.forward_hip(tensors[:n_inputs], state)
+        ctx.mapper, ctx.state, ctx.names, ctx.splits, ctx.n_inputs = mapper, state, names, splits, n_inputs
+        mapper.__dict__["_train_state_ref"] = weakref.ref(state)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *cotangents):
+        wanted = ctx.needs_input_grad[4:4 + ctx.n_inputs]
+        grads, dxs = ctx.mapper._run_backward(ctx.state, cotangents, wanted, ctx.splits)
+        return (None, None, None, None) + tuple(dxs) + tuple(grads.get(n) for n in ctx.names)

@@ -5,7 +5,9 @@
 //                               per image on the matrix cores; the 1x1 epilogue writes NCHW and per-(image, channel,
 //                               pixel tile) GroupNorm partials (mean, M2); the 3x3 level is split over K into partial sums
 //   frontend_groupnorm_kernel   every level in one launch: merges the partials in a fixed order (Chan's formula, no
-//                               atomics), reduces the 3x3 split-K sums, applies (x - mean) * rstd * gamma + beta in place
+//                               atomics), reduces the 3x3 split-K sums, applies (x - mean) * rstd * gamma + beta in place;
+//                               <true> is the training forward's (sdetr_frontend_groupnorm_train): it also keeps the raw
+//                               convolution and the statistics for frontend_backward.hip
 //   frontend_positions_kernel   all levels' nearest-down-sampled masks and sine position maps in one launch
 //
 // GEMM tiles: 128 output channels x 128 pixels x 32 reduction indices, 4 waves of 64 x 64 (2 x 2 v_mfma_f32_32x32x16 per
@@ -322,6 +324,8 @@ struct NormLevel {
     float *out;              // [B, Co, P], normalised in place (3x3: written here from the partials)
     const float *part;       // 1x1: stats [B][Co][tiles_n][2]; 3x3: split sums [S][B][Co][P]
     const float *gamma, *beta;
+    float *z;                // training forward: the raw convolution [B, Co, P] (a buffer of its own)
+    float *stats;            // training forward: [B][groups][2] = (mean, rstd)
     int P, kernel, tiles_n, splits, chunks;
     int block0;
 };
@@ -348,6 +352,9 @@ __device__ __forceinline__ void block_merge(float &mean, float &m2, float &n, fl
     mean = red[0]; m2 = red[kFThreads]; n = red[2 * kFThreads];
 }
 
+// TRAIN: the same arithmetic in the same order (the output is bit-identical), and what the backward reads on the side:
+// the raw convolution to L.z and the group's (mean, rstd) to L.stats
+template <bool TRAIN>
 __global__ void __launch_bounds__(kFThreads) frontend_groupnorm_kernel(NormArgs p)
 {
     __shared__ float red[3 * kFThreads];
@@ -362,6 +369,7 @@ __global__ void __launch_bounds__(kFThreads) frontend_groupnorm_kernel(NormArgs 
     const int cg = p.co / p.groups, tid = threadIdx.x;
     const int64_t glen = (int64_t)cg * L.P;
     float *y = L.out + ((int64_t)img * p.co + (int64_t)g * cg) * L.P;   // the group's channels are contiguous
+    float *zs = TRAIN ? L.z + ((int64_t)img * p.co + (int64_t)g * cg) * L.P : nullptr;
     float mean = 0.f, m2 = 0.f, n = 0.f;
     if (L.kernel == 1) {
         const int items = cg * L.tiles_n;
@@ -378,6 +386,7 @@ __global__ void __launch_bounds__(kFThreads) frontend_groupnorm_kernel(NormArgs 
             float v = 0.f;
             for (int s = 0; s < L.splits; ++s) v += src[s * split_stride + e];
             y[e] = v;
+            if (TRAIN) zs[e] = v;
             n += 1.f;
             const float d = v - mean;
             mean += d / n;
@@ -392,9 +401,16 @@ __global__ void __launch_bounds__(kFThreads) frontend_groupnorm_kernel(NormArgs 
         e1 = min(glen, e0 + kFNormChunk);
     }
     // (3x3: each thread re-reads exactly the elements it wrote above)
+    if (TRAIN && chunk == 0 && tid == 0) {
+        float *st = L.stats + ((int64_t)img * p.groups + g) * 2;
+        st[0] = mean;
+        st[1] = rstd;
+    }
     for (int64_t e = e0 + tid; e < e1; e += kFThreads) {
         const int c = g * cg + (int)(e / L.P);
-        y[e] = (y[e] - mean) * rstd * L.gamma[c] + L.beta[c];
+        const float v = y[e];
+        if (TRAIN && L.kernel == 1) zs[e] = v;
+        y[e] = (v - mean) * rstd * L.gamma[c] + L.beta[c];
     }
 }
 
@@ -605,11 +621,11 @@ extern "C" int sdetr_frontend_conv(sdetr_stream_t stream, const sdetr_frontend_l
     return check_launch(what);
 }
 
-extern "C" int sdetr_frontend_groupnorm(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
-                                        int out_channels, int num_groups, float eps, const void *workspace,
-                                        int64_t workspace_bytes)
+// the one GroupNorm launch; z / stats (host arrays of n_levels device pointers) make it the training forward's
+static int launch_groupnorm(const char *what, sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
+                            int out_channels, int num_groups, float eps, const void *workspace, int64_t workspace_bytes,
+                            float *const *z, float *const *stats)
 {
-    const char *what = "frontend_groupnorm";
     Plan pl;
     if (int rc = make_plan(what, levels, n_levels, batch, out_channels, pl)) return rc;
     if (num_groups < 1 || out_channels % num_groups)
@@ -627,14 +643,36 @@ extern "C" int sdetr_frontend_groupnorm(sdetr_stream_t stream, const sdetr_front
         n.out = L.out;
         n.part = reinterpret_cast<const float *>(static_cast<const char *>(workspace) + pl.ws_off[i]);
         n.gamma = L.gamma; n.beta = L.beta;
+        if (z) {
+            if (!z[i] || !stats[i] || z[i] == L.out) return fail("%s: level %d: null z or stats, or z aliases out", what, i);
+            n.z = z[i]; n.stats = stats[i];
+        }
         n.P = pl.ho[i] * pl.wo[i]; n.kernel = L.kernel_size; n.tiles_n = pl.tiles_n[i]; n.splits = pl.splits[i];
         n.chunks = L.kernel_size == 1 ? (int)(((int64_t)cg * n.P + kFNormChunk - 1) / kFNormChunk) : 1;
         n.block0 = (int)blocks;
         blocks += (int64_t)batch * num_groups * n.chunks;
         if (blocks > 0x7fffffffLL) return fail("%s: too many workgroups", what);
     }
-    hipLaunchKernelGGL(frontend_groupnorm_kernel, dim3((unsigned)blocks), dim3(kFThreads), 0, (hipStream_t)stream, a);
+    if (z) hipLaunchKernelGGL(frontend_groupnorm_kernel<true>, dim3((unsigned)blocks), dim3(kFThreads), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(frontend_groupnorm_kernel<false>, dim3((unsigned)blocks), dim3(kFThreads), 0, (hipStream_t)stream, a);
     return check_launch(what);
+}
+
+extern "C" int sdetr_frontend_groupnorm(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels, int batch,
+                                        int out_channels, int num_groups, float eps, const void *workspace,
+                                        int64_t workspace_bytes)
+{
+    return launch_groupnorm("frontend_groupnorm", stream, levels, n_levels, batch, out_channels, num_groups, eps, workspace,
+                            workspace_bytes, nullptr, nullptr);
+}
+
+extern "C" int sdetr_frontend_groupnorm_train(sdetr_stream_t stream, const sdetr_frontend_level *levels, int n_levels,
+                                              int batch, int out_channels, int num_groups, float eps, const void *workspace,
+                                              int64_t workspace_bytes, float *const *z, float *const *stats)
+{
+    if (!z || !stats) return fail("frontend_groupnorm_train: null z or stats array");
+    return launch_groupnorm("frontend_groupnorm_train", stream, levels, n_levels, batch, out_channels, num_groups, eps,
+                            workspace, workspace_bytes, z, stats);
 }
 
 extern "C" int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, int batch, int height, int width,
