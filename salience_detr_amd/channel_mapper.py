@@ -27,7 +27,9 @@ bit, which also keeps the raw convolution ``z`` and every group's (mean, rstd) -
 maps and the trainable parameters.  Its backward is one ``sdetr_frontend_bwd_run`` plan (``build_backward_plan``), levels
 from the last to the first: the GroupNorm backward (from ``z`` and the statistics, never from the output: gamma may be
 zero), the backbone's backward-weight and backward-data kernels on its channels-last result, and one egest per input that
-requires grad, back to fp32 NCHW.  Stored: ``z``, the statistics and the inputs themselves (no copy).  Served:
+requires grad, back to fp32 NCHW.  Stored: ``z``, the statistics and the inputs themselves (no copy; an input that is not
+dense fp32 NCHW -- a torch-form ConvNeXt hands out channels-last maps -- is copied once, in the inference form too, and the
+copy is what is stored and read; its gradient comes back dense, in the input's shape).  Served:
 ``hip_form()``, ``out_channels % 8 == 0``, float32 or bfloat16, HIP tensors; anything else raises at forward with the reason
 (``hip_train_reason``), it never falls back.
 """
@@ -201,10 +203,14 @@ class ChannelMapper(nn.Module):
                         gn.eps, ws.data_ptr(), ws_bytes, what="ChannelMapper (groupnorm)")
 
     def _check_inputs(self, inputs: Sequence[Tensor]) -> List[Tensor]:
+        """The inputs as the kernels read them: fp32, dense NCHW, on the device.  A map of another dtype or in other
+        strides (a torch-form backbone hands out channels-last maps) is copied; a contiguous fp32 one is taken as it is."""
         xs = []
         for x in inputs:
             if x.dtype != torch.float32:
                 x = x.float()
+            if not x.is_contiguous():
+                x = x.contiguous()
             _hip.require_device("ChannelMapper", x=x)
             xs.append(x)
         for p in self.parameters():
