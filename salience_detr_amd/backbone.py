@@ -14,7 +14,7 @@ How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/
     and the ReLU; the weight is folded and packed once per parameter version (``derived``);
   * activations between layers are channels-last in the compute dtype; the last block of each returned stage also
     writes the stage's fp32 NCHW map; the stem reads the fp32 NCHW canvas; the max pool is a launch of its own;
-  * the whole network is one precomputed plan (``build_plan``, filled through ``backbone_base.PlanBuilder`` as the other
+  * the whole network is one precomputed plan (``build_plan``, filled through ``hip_module.PlanBuilder`` as the other
     backbones' are) handed to ``sdetr_backbone_run`` (one ctypes call per forward);
   * ``set_dtype``: fp32 (default) multiplies at fp32 accuracy (exact three-way bf16 split of both operands); bf16 /
     fp16 take one 16-bit product with fp32 accumulation and keep the activations in that type between layers.
@@ -23,10 +23,10 @@ The HIP path serves every ``groups == 1`` arch without dilation or DCN: resnet18
 plain-torch composite (``F.conv2d`` + the frozen affine), which is also the default autograd path.  A CPU tensor on the
 HIP form raises: the hot path has no CPU fallback.
 
-Training in HIP (``set_train_form("hip")``, ``csrc/backbone_backward.hip``; the interface and its autograd node are
-``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored activations and ``_run_backward``): a forward
-that needs autograd runs the same forward plan inside one autograd node; its backward is one ``sdetr_backbone_bwd_run``
-call over ``build_backward_plan``:
+Training in HIP (``set_train_form("hip")``, ``csrc/backbone_backward.hip``; the interface, its autograd node and
+``_run_backward`` are ``backbone_base.HipBackbone``'s, this module gives ``_trainable``, the stored activations and
+``_backward_ops``): a forward that needs autograd runs the same forward plan inside one autograd node; its backward is one
+``sdetr_backbone_bwd_run`` call over ``build_backward_plan``:
 one backward-data launch per conv whose input has a trainable conv upstream, one backward-weight launch per trainable
 conv (plus the fixed-order reduction where a reduction is split), one ingest launch per returned map.  The stored
 activations are the ReLU masks and the weight-gradient operands; no activation is copied.  Served: ``hip_form()``
@@ -40,8 +40,9 @@ import torch
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import HipBackbone, PlanBuilder
+from .backbone_base import HipBackbone
 from .derived import derived
+from .hip_module import PlanBuilder
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -295,23 +296,16 @@ class ResNetBackbone(HipBackbone):
                 outs[f"layer{i + 1}"] = x
         return outs
 
-    def _packed(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d, layout: int) -> Tuple[Tensor, Tensor]:
+    def _packed_conv_bn(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d, layout: int) -> Tuple[Tensor, Tensor]:
         """``(packed weight, folded bias)`` of ``conv`` + ``bn`` (``sdetr_backbone_pack``), built once per parameter
         version, precision and compute dtype."""
-        precision, lib = self._precision(), self._lib()
-        co, ci, k = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+        sources = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
 
         def build():
-            f32 = [t.detach().to(torch.float32).contiguous() for t in
-                   (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-            nbytes = lib.sdetr_backbone_packed_bytes(co, ci, k, precision)
-            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=f32[0].device)
-            bias = torch.empty(co, dtype=torch.float32, device=f32[0].device)
-            _hip.launch("sdetr_backbone_pack", lib, f32[0].device, *[t.data_ptr() for t in f32], float(bn.eps), co, ci, k,
-                        layout, precision, packed.data_ptr(), bias.data_ptr(), what="ResNetBackbone (pack)")
-            return packed, bias
-        return derived(conv, "backbone_packed", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build,
-                       extra=(float(bn.eps), precision, self.compute_dtype, layout))
+            f32 = [t.detach().to(torch.float32).contiguous() for t in sources]
+            return self._pack(f32[0], f32[1:], float(bn.eps), layout)
+        return derived(conv, "backbone_packed", sources, build,
+                       extra=(float(bn.eps), self._precision(), self.compute_dtype, layout))
 
     def build_plan(self, x: Tensor, splits: int = 0, acts: Optional[Dict[str, Tensor]] = None):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
@@ -327,7 +321,7 @@ class ResNetBackbone(HipBackbone):
         def conv_op(conv, bn, src, h, w, relu, residual=None, nchw_out=None, x_nchw=False):
             k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
             ho, wo = _out_hw(h, k, s, p), _out_hw(w, k, s, p)
-            packed, bias = self._packed(conv, bn, 1 if x_nchw else 0)
+            packed, bias = self._packed_conv_bn(conv, bn, 1 if x_nchw else 0)
             keep.extend((packed, bias))
             out = new((batch, ho, wo, conv.out_channels), act)
             if acts is not None:
@@ -382,7 +376,7 @@ class ResNetBackbone(HipBackbone):
 
     # ------------------------------------------------------------------------------------------ training in HIP
     # (the interface is HipBackbone's: the node keeps the plan's channels-last activations; its backward runs
-    # ``build_backward_plan`` with one ``sdetr_backbone_bwd_run`` call and returns the fp32 weight gradients)
+    # ``_backward_ops`` with one ``sdetr_backbone_bwd_run`` call and returns the fp32 weight gradients)
     train_reasons = ("the architecture is not one the HIP kernels serve (grouped / dilated convs, a bias or a norm layer "
                      "other than FrozenBatchNorm2d)",
                      "the stem (conv1) is not frozen: the stem and max-pool backward are out of scope")
@@ -477,21 +471,12 @@ class ResNetBackbone(HipBackbone):
     def _packed_dgrad(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d, with_weight: bool) -> Tuple[Optional[Tensor], Tensor]:
         """``(backward-data packed weight, s[out])`` of ``conv`` + ``bn`` (``sdetr_backbone_pack_dgrad``), built once per
         parameter version, precision and compute dtype; without ``with_weight`` only the scale."""
-        precision, lib = self._precision(), self._lib()
-        co, ci, k = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+        sources = (conv.weight, bn.weight, bn.running_var)
 
         def build():
-            f32 = [t.detach().to(torch.float32).contiguous() for t in (conv.weight, bn.weight, bn.running_var)]
-            packed = None
-            if with_weight:
-                nbytes = lib.sdetr_backbone_dgrad_packed_bytes(co, ci, k, precision)
-                packed = torch.empty(nbytes // 2, dtype=torch.int16, device=f32[0].device)
-            scale = torch.empty(co, dtype=torch.float32, device=f32[0].device)
-            _hip.launch("sdetr_backbone_pack_dgrad", lib, f32[0].device, *[t.data_ptr() for t in f32], float(bn.eps), co,
-                        ci, k, precision, _hip.ptr(packed), scale.data_ptr(), what="ResNetBackbone (pack dgrad)")
-            return packed, scale
-        return derived(conv, "backbone_packed_dgrad" if with_weight else "backbone_bn_scale",
-                       (conv.weight, bn.weight, bn.running_var), build, extra=(float(bn.eps), precision, self.compute_dtype))
+            return self._pack_dgrad(*[t.detach().to(torch.float32).contiguous() for t in sources], float(bn.eps), with_weight)
+        return derived(conv, "backbone_packed_dgrad" if with_weight else "backbone_bn_scale", sources, build,
+                       extra=(float(bn.eps), self._precision(), self.compute_dtype))
 
     def _trainable_convs(self) -> List[Tuple[str, nn.Conv2d]]:
         return [(n, m) for n, m in self.named_modules() if isinstance(m, nn.Conv2d) and m.weight.requires_grad]
@@ -505,47 +490,45 @@ class ResNetBackbone(HipBackbone):
         forward's autograd graph is alive."""
         return [(n, t) for n, t in self._train_state()["acts"].items() if n != "pool" and ".downsample." not in n]
 
-    def _run_backward(self, state: dict, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0
-                      ) -> Dict[str, Tensor]:
-        """Runs the backward plan on the stored activations; returns ``{conv name: fp32 weight gradient}``."""
+    backward_struct, backward_prefix = _hip.BackboneBwdOpStruct, "sdetr_backbone_bwd"
+
+    def _backward_ops(self, acts: Dict[str, Tensor], factors, shape, cotangents: Dict[str, Optional[Tensor]], splits: int = 0):
+        """The name records of ``build_backward_plan`` as ops on the stored activations: ``(ops, names, grads, keep)``,
+        ``grads`` being ``{conv name: fp32 weight gradient}``."""
         batch, _, height, width = shape
-        plan = self.build_backward_plan(batch, height, width)
         modules = dict(self.named_modules())
-        acts = state["acts"]
-        dev = acts["pool"].device
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
+        pb = PlanBuilder(_hip.BackboneBwdOpStruct, acts["pool"], batch=batch, splits=splits)
         tensors: Dict[str, Tensor] = dict(acts)
-        keep: List[Tensor] = []
-        kinds = {"dgrad": 0, "wgrad": 1, "ingest": 2}
-        ops = []
-        for d in plan:
+        grads: Dict[str, Tensor] = {}
+        for d in self.build_backward_plan(batch, height, width):
             weight = scale = None
+            rows = (batch, d["height"], d["width"], d["in_channels"])
             if d["kind"] == "ingest":
                 g = cotangents.get(d["conv"])
-                shape_nchw = (batch, d["in_channels"], d["height"], d["width"])
-                g = torch.zeros(shape_nchw, device=dev) if g is None else g.to(torch.float32).contiguous()
+                if g is None:
+                    g = torch.zeros((batch, d["in_channels"], d["height"], d["width"]), device=pb.device)
+                g = g.to(torch.float32).contiguous()
+                pb.keep.append(g)
                 tensors[d["dz"]] = g
-                out_shape = (batch, d["height"], d["width"], d["in_channels"])
-                tensors[d["out"]] = torch.empty(out_shape, device=dev, dtype=act)
+                out = pb.new(rows, act)
             else:
                 conv = modules[d["conv"]]
                 bn = modules[d["conv"][:-len("conv1")] + "bn" + d["conv"][-1]] if ".downsample." not in d["conv"] \
                     else modules[d["conv"][:-1] + "1"]
                 if d["kind"] == "wgrad":
                     scale = self._packed_dgrad(conv, bn, False)[1]
-                    tensors[d["out"]] = torch.empty(conv.weight.shape, device=dev, dtype=torch.float32)
+                    out = grads[d["conv"]] = pb.new(conv.weight.shape, torch.float32)
                 else:
                     weight = self._packed_dgrad(conv, bn, True)[0]
-                    tensors[d["out"]] = torch.empty((batch, d["height"], d["width"], d["in_channels"]), device=dev, dtype=act)
-                keep.extend(t for t in (weight, scale) if t is not None)
-            ops.append(_hip.BackboneBwdOpStruct(
-                kind=kinds[d["kind"]], dz=tensors[d["dz"]].data_ptr(), x=_hip.ptr(tensors.get(d["x"])), weight=_hip.ptr(weight),
-                scale=_hip.ptr(scale), add=_hip.ptr(tensors.get(d["add"])), mask=_hip.ptr(tensors.get(d["mask"])),
-                out=tensors[d["out"]].data_ptr(), batch=batch, splits=splits,
-                **{f: d[f] for f in ("in_channels", "height", "width", "out_channels", "kernel_size", "stride", "padding")}))
-        if ops:
-            self._run_plan(_hip.BackboneBwdOpStruct, "sdetr_backbone_bwd", ops, dev)
-        return {d["conv"]: tensors[d["out"]] for d in plan if d["kind"] == "wgrad"}
+                    out = pb.new(rows, act)
+                pb.keep.append(scale if weight is None else weight)
+            tensors[d["out"]] = out
+            pb.op(f"{d['conv']} ({d['kind']})", {"dgrad": 0, "wgrad": 1, "ingest": 2}[d["kind"]], dz=tensors[d["dz"]].data_ptr(),
+                  x=_hip.ptr(tensors.get(d["x"])), weight=_hip.ptr(weight), scale=_hip.ptr(scale),
+                  add=_hip.ptr(tensors.get(d["add"])), mask=_hip.ptr(tensors.get(d["mask"])), out=out.data_ptr(),
+                  **{f: d[f] for f in ("in_channels", "height", "width", "out_channels", "kernel_size", "stride", "padding")})
+        return pb.ops, pb.names, grads, pb.keep
 
 
 def batch_images(images: Sequence[Tensor], size_divisible: int = 32, normalize: bool = True,

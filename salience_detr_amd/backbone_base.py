@@ -1,13 +1,10 @@
-"""What the four HIP backbones (``backbone.py``, ``convnext.py``, ``focalnet.py``, ``swin.py``) share: ``HipBackbone``,
-the module base with the precision switch, the torch / HIP dispatch, checkpoint loading, the operand packers, the
-launch of a plan, the opening checks of a ``forward_hip`` and the training interface (``set_train_form``,
-``hip_train_reason``, ``forward_hip_train`` and the one autograd node behind it: a backbone with a HIP backward adds its
-forward's stored state and either ``_sequence`` and ``_backward_ops``, which the default ``_run_backward`` runs, or a
-``_run_backward`` of its own); ``PlanBuilder``, the op list a ``build_plan`` fills, with the stochastic-depth draw;
-``BackwardPlanBuilder``, the op list, gradients, scratch buffers and shared emitters a ``_backward_ops`` fills; and the
-two parameter-free holder modules ``Permute`` and ``StochasticDepth``."""
+"""What the four HIP backbones (``backbone.py``, ``convnext.py``, ``focalnet.py``, ``swin.py``) share on top of
+``hip_module.HipModule``: ``HipBackbone``, with the torch / HIP dispatch, checkpoint loading, the operand packers, the
+opening checks of a ``forward_hip`` and a backbone's side of the training interface (``hip_train_reason``,
+``forward_hip_train`` and the autograd node's hooks: a backbone with a HIP backward adds its forward's stored state and a
+``_backward_ops``, which the default ``_run_backward`` runs); and the two parameter-free holder modules ``Permute`` and
+``StochasticDepth``."""
 import os
-import weakref
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -15,6 +12,7 @@ from torch import Tensor, nn
 
 from . import _hip
 from .derived import derived
+from .hip_module import HipModule, _TrainFunction
 
 
 class Permute(nn.Module):
@@ -52,183 +50,18 @@ class StochasticDepth(nn.Module):
         return f"{self.__class__.__name__}(p={self.p}, mode={self.mode})"
 
 
-class PlanBuilder:
-    """The op list of one forward: ``ops`` (structs of ``struct_type``), ``names`` (one label per op), ``keep`` (every
-    tensor the ops point into) and ``outputs`` (the returned maps).  ``defaults`` are the fields every op of the plan
-    starts from (the batch, the splits ..); the struct's remaining fields start at zero / null.  An op's kind goes into
-    the struct's first field, whatever the header calls it (``kind``, or ``op`` in ``sdetr_backbone_op``)."""
-
-    def __init__(self, struct_type, x: Tensor, **defaults):
-        self.struct_type, self.device, self.defaults = struct_type, x.device, defaults
-        self.kind_field = struct_type._fields_[0][0]
-        self.ops: list = []
-        self.names: List[str] = []
-        self.keep: List[Tensor] = [x]
-        self.outputs: Dict[str, Tensor] = {}
-
-    def new(self, shape, dtype) -> Tensor:
-        t = torch.empty(shape, device=self.device, dtype=dtype)
-        self.keep.append(t)
-        return t
-
-    def op(self, name: str, kind: int, **fields):
-        self.ops.append(self.struct_type(**{self.kind_field: kind, **self.defaults, **fields}))
-        self.names.append(name)
-
-    def layer_norm(self, name: str, kind: int, affine: Tuple[Tensor, Tensor], eps: float, src: Tensor, out: Tensor, h: int,
-                   w: int, c: int, out_f32: bool = False, **fields):
-        """LayerNorm over the ``c`` channels of the fp32 rows ``src`` ``[batch, h, w, c]`` into ``out``."""
-        gamma, beta = affine
-        self.keep.extend((gamma, beta))
-        self.op(name, kind, x=src.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), out=out.data_ptr(), in_channels=c,
-                height=h, width=w, out_channels=c, out_f32=1 if out_f32 else 0, eps=float(eps), **fields)
-
-    def draw(self, sd: StochasticDepth, batch: int, training_forward: bool) -> Optional[Tensor]:
-        """``StochasticDepth.forward``'s own draw, in its order: the factors ``[batch, 1, 1, 1]`` (0 or 1 / (1 - p)) of
-        one residual branch; ``None`` when nothing is drawn (inference, ``eval()`` or ``p == 0``)."""
-        if not training_forward or not sd.training or sd.p == 0.0:
-            return None
-        factor = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=self.device).bernoulli_(1.0 - sd.p)
-        if sd.p < 1.0:
-            factor.div_(1.0 - sd.p)
-        self.keep.append(factor)
-        return factor
-
-
-class BackwardPlanBuilder(PlanBuilder):
-    """The op list of one backward over rows ``[batch, h, w, c]``: ``grads`` (``{parameter name: fp32 tensor}``, as views
-    of what the ops write), the scratch buffers and one emitter per kind that ``sdetr_convnext_bwd_op`` and
-    ``sdetr_swin_bwd_op`` number alike (0 dgrad, 1 wgrad, 2 rows, 3 gelu, 4 layer norm); the NCHW ingest has the caller's
-    number.  An op's name is its label in the op-timing tools."""
-
-    def __init__(self, struct_type, x: Tensor, **defaults):
-        super().__init__(struct_type, x, **defaults)
-        self.grads: Dict[str, Tensor] = {}
-        self.scratch: Dict[tuple, Tensor] = {}
-        self.flip = 0
-
-    def tmp(self, tag: str, shape, dtype) -> Tensor:
-        """A buffer the next block may overwrite: the plan runs in order on one stream."""
-        key = (tag, tuple(shape), dtype)
-        if key not in self.scratch:
-            self.scratch[key] = self.new(shape, dtype)
-        return self.scratch[key]
-
-    def ones(self, n: int) -> Tensor:
-        key = ("ones", n)
-        if key not in self.scratch:
-            self.scratch[key] = torch.ones(n, device=self.device)
-            self.keep.append(self.scratch[key])
-        return self.scratch[key]
-
-    @staticmethod
-    def want(*params) -> bool:
-        return any(p is not None and p.requires_grad for p in params)
-
-    def grad(self, name: str, shape, *params) -> Optional[Tensor]:
-        """The fp32 gradient buffer of parameter ``name`` when one of ``params`` requires it, else ``None``."""
-        if not self.want(*params):
-            return None
-        self.grads[name] = self.new(shape, torch.float32)
-        return self.grads[name]
-
-    def next_dy(self, shape) -> Tensor:
-        """The stream's gradient below the current module: two fp32 buffers in turns."""
-        dy = self.tmp(f"dy{self.flip}", shape, torch.float32)
-        self.flip ^= 1
-        return dy
-
-    def wgrad(self, name: str, dz: Tensor, x: Tensor, ci: int, co: int, h: int, w: int) -> Tensor:
-        """``dW [co, ci] = dz^T x`` of a Linear, registered as ``<name>.weight``."""
-        dw = self.grads[name + ".weight"] = self.new((co, ci), torch.float32)
-        self.op(name + " (wgrad)", 1, dz=dz.data_ptr(), x=x.data_ptr(), scale=self.ones(co).data_ptr(), out=dw.data_ptr(),
-                channels=ci, height=h, width=w, out_channels=co)
-        return dw
-
-    def dgrad(self, name: str, packed: Tensor, dz: Tensor, out: Tensor, ci: int, co: int, h: int, w: int):
-        """``out = dz W`` over the ``_packed_rows_dgrad`` planes of a Linear's weight."""
-        self.keep.append(packed)
-        self.op(name + " (dgrad)", 0, dz=dz.data_ptr(), weight=packed.data_ptr(), out=out.data_ptr(), channels=ci, height=h,
-                width=w, out_channels=co)
-
-    def rows(self, name: str, dz: Tensor, factor: Optional[Tensor], out: Tensor, dbias: Optional[Tensor], c: int, h: int,
-             w: int):
-        """``out = factor[n] * dz`` in ``out``'s type and the column sums of it (a bias gradient) into ``dbias``."""
-        self.op(name + " (rows)", 2, dz=dz.data_ptr(), scale=_hip.ptr(factor), out=out.data_ptr(), dbias=_hip.ptr(dbias),
-                channels=c, height=h, width=w)
-
-    def gelu(self, name: str, dz: Tensor, pre: Tensor, dbias: Optional[Tensor], c: int, h: int, w: int):
-        """``dz *= gelu'(pre)`` in place and the column sums of it (the bias gradient of the Linear in front)."""
-        self.op(name + " (gelu)", 3, dz=dz.data_ptr(), x=pre.data_ptr(), out=dz.data_ptr(), dbias=_hip.ptr(dbias), channels=c,
-                height=h, width=w)
-
-    def layer_norm_bwd(self, name: str, norm: nn.LayerNorm, gamma32: Tensor, kind: int = 4, label: str = " (layer norm)",
-                       **fields):
-        """A LayerNorm backward (kind 4, or a backbone's own variant of it); ``fields`` are the op's remaining ones,
-        tensors for its pointers.  Registers ``<name>.weight`` / ``<name>.bias``."""
-        self.keep.append(gamma32)
-        n = norm.weight.numel()
-        affine = self.want(norm.weight, norm.bias)
-        dgam = self.new((n,), torch.float32) if affine else None
-        dbet = self.new((n,), torch.float32) if affine else None
-        fields = {k: v.data_ptr() if isinstance(v, Tensor) else v for k, v in fields.items()}
-        self.op(name + label, kind, gamma=gamma32.data_ptr(), dgamma=_hip.ptr(dgam), dbeta=_hip.ptr(dbet), eps=float(norm.eps),
-                **fields)
-        if self.want(norm.weight):
-            self.grads[name + ".weight"] = dgam
-        if self.want(norm.bias):
-            self.grads[name + ".bias"] = dbet
-
-    def ingest(self, name: str, kind: int, cotangent: Optional[Tensor], add: Optional[Tensor], c: int, h: int, w: int) -> Tensor:
-        """A returned map's NCHW cotangent plus ``add`` (what arrives from above) as fp32 rows; ``add`` itself when the
-        map has no cotangent."""
-        if cotangent is None and add is not None:
-            return add
-        batch = self.defaults["batch"]
-        g = torch.zeros((batch, c, h, w), device=self.device) if cotangent is None else cotangent.to(torch.float32).contiguous()
-        self.keep.append(g)
-        out = self.new((batch, h, w, c), torch.float32)
-        self.op(name + " (ingest)", kind, dz=g.data_ptr(), add=_hip.ptr(add), out=out.data_ptr(), channels=c, height=h, width=w)
-        return out
-
-
-class _TrainState(dict):
-    """What one ``"hip"`` training forward stored for its backward; a dict that can be weakly referenced."""
-
-
-class _TrainFunction(torch.autograd.Function):
-    """``HipBackbone.forward_hip_train``: inputs are the trainable parameters, outputs the returned fp32 maps."""
-
-    @staticmethod
-    def forward(ctx, backbone: "HipBackbone", x: Tensor, splits: int, names: Tuple[str, ...], *params: Tensor):
-        state = _TrainState()
-        outputs = backbone.forward_hip(x, splits, state)
-        ctx.backbone, ctx.state, ctx.names, ctx.splits = backbone, state, names, splits
-        ctx.shape = tuple(x.shape)
-        ctx.keys = sorted(outputs)
-        backbone.__dict__["_train_state_ref"] = weakref.ref(state)
-        return tuple(outputs[k] for k in ctx.keys)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        got = ctx.backbone._run_backward(ctx.state, ctx.shape, dict(zip(ctx.keys, grads)), ctx.splits)
-        return (None, None, None, None) + tuple(None if n not in got else got[n].contiguous() for n in ctx.names)
-
-
-class HipBackbone(nn.Module):
+class HipBackbone(HipModule):
     """A backbone with a HIP inference form (``forward_hip``, one plan per forward) and a plain-torch composite
     (``forward_torch``, the autograd path); a subclass gives both, ``hip_form()`` and ``compute_dtype``.
 
     One with a HIP backward also gives ``train_reasons`` and ``_stem_modules()`` (what ``hip_train_reason`` says in its
-    own words), ``_output_name(i)`` and ``forward_hip(x, splits, state)`` (``state``, a dict, receives what the backward
-    reads).  The rest has a default here for a backbone whose backward walks ``_sequence()`` (``[(kind, name, module)]``
-    in forward order) in ``_backward_ops`` (a ``BackwardPlanBuilder``'s ``(ops, names, grads, keep)``), run as
-    ``backward_struct`` ops by ``<backward_prefix>_run``: ``_trainable()`` (``[(name, tensor)]``: the autograd node's
-    inputs), ``_first_trainable()``, the test hooks and ``_run_backward(state, shape, cotangents, splits)`` (``{name:
-    fp32 gradient}``).  The ResNet, whose backward plan goes by tensor names, overrides them."""
+    own words), ``_output_name(i)``, ``forward_hip(x, splits, state)`` (``state``, a dict, receives what the backward
+    reads) and ``_backward_ops(acts, factors, shape, cotangents, splits)`` (``(ops, names, grads, keep)``, filled through
+    a ``PlanBuilder``), run as ``backward_struct`` ops by ``<backward_prefix>_run``.  The rest has a default here:
+    ``_trainable()`` (``[(name, tensor)]``: the autograd node's inputs), the test hooks, ``_run_backward(state, shape,
+    cotangents, splits)`` (``{name: fp32 gradient}``) and, for a backbone whose backward walks ``_sequence()`` (``[(kind,
+    name, module)]`` in forward order), ``_first_trainable()``."""
 
-    train_form = "torch"
     # of a backbone with a HIP backward: why hip_form() is False, why a trainable stem is not served
     train_reasons: Optional[Tuple[str, str]] = None
     # of the default _run_backward: the backward op struct and the C prefix of its entry points
@@ -259,19 +92,6 @@ class HipBackbone(nn.Module):
         matched = {k: v for k, v in weights.items() if k not in own or own[k].shape == v.shape}
         return self.load_state_dict(matched, strict=False)
 
-    def set_dtype(self, dtype: torch.dtype):
-        """Precision of the products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or ``torch.float16`` (one
-        16-bit product, fp32 accumulation, 16-bit GEMM operands between launches).  Outputs are fp32."""
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError(f"{type(self).__name__}.set_dtype: {dtype} is not float32 / bfloat16 / float16")
-        self.compute_dtype = dtype
-        return self
-
-    def _needs_autograd(self, x: Tensor) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        return x.requires_grad or any(p.requires_grad for p in self.parameters())
-
     def forward(self, x: Tensor) -> Dict[str, Tensor]:
         if self.train_form == "hip" and self._needs_autograd(x):
             return self.forward_hip_train(x)
@@ -280,16 +100,6 @@ class HipBackbone(nn.Module):
         return self.forward_hip(x)
 
     # ------------------------------------------------------------------------------------------ training in HIP
-    def set_train_form(self, form: str):
-        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
-        (the HIP forward plan inside an autograd node whose backward is one plan too, see ``forward_hip_train``).
-        ``"hip"`` on a module or input that is not eligible (``hip_train_reason``) raises at forward: it never falls
-        back."""
-        if form not in ("torch", "hip"):
-            raise ValueError(f"{type(self).__name__}.set_train_form: {form!r} is not 'torch' / 'hip'")
-        self.train_form = form
-        return self
-
     def _stem_modules(self) -> Sequence[nn.Module]:
         """The modules below the first stage, whose backward is out of scope."""
         return ()
@@ -315,29 +125,23 @@ class HipBackbone(nn.Module):
             return "the input requires a gradient: the gradient to the image is out of scope"
         return None
 
-    def hip_train_form(self, x: Optional[Tensor] = None) -> bool:
-        """True when ``set_train_form("hip")`` can train this module (on input ``x``): ``hip_form()``, a frozen stem, an
-        input without gradient and a float32 / bfloat16 compute dtype."""
-        return self.hip_train_reason(x) is None
-
     def forward_hip_train(self, x: Tensor, splits: int = 0) -> Dict[str, Tensor]:
         """The ``"hip"`` training form: the HIP forward plan as one autograd node.  The node keeps what the backward
         reads (the plan's own activations, no copy); its backward is one ``_run_backward`` call and returns the fp32
         parameter gradients to autograd, which accumulates them into ``.grad``."""
-        reason = self.hip_train_reason(x)
-        if reason is not None:
-            raise RuntimeError(f"{type(self).__name__}: the 'hip' training form cannot run: {reason}")
+        self._check_train_form(x)
         named = self._trainable()
-        maps = _TrainFunction.apply(self, x, splits, tuple(n for n, _ in named), *[t for _, t in named])
+        maps = _TrainFunction.apply(self, 1, splits, tuple(n for n, _ in named), x, *[t for _, t in named])
         return dict(zip([self._output_name(i) for i in sorted(self.return_indices)], maps))
 
-    def _train_state(self) -> dict:
-        """What the last ``"hip"`` training forward stored; valid while that forward's autograd graph is alive."""
-        state = self.__dict__.get("_train_state_ref")
-        state = state() if state is not None else None
-        if state is None:
-            raise RuntimeError(f"{type(self).__name__}: no 'hip' training forward is alive")
-        return state
+    def _train_forward(self, inputs: Sequence[Tensor], splits: int, state: dict) -> Tuple[Tensor, ...]:
+        outputs = self.forward_hip(inputs[0], splits, state)
+        state["shape"], state["keys"] = tuple(inputs[0].shape), sorted(outputs)
+        return tuple(outputs[k] for k in state["keys"])
+
+    def _train_backward(self, state: dict, cotangents: Sequence[Optional[Tensor]], wanted: Sequence[bool], splits: int):
+        """(No gradient for the image: ``hip_train_reason`` refuses one that requires it.)"""
+        return self._run_backward(state, state["shape"], dict(zip(state["keys"], cotangents)), splits), (None,)
 
     def _trainable(self) -> List[Tuple[str, Tensor]]:
         return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
@@ -348,11 +152,6 @@ class HipBackbone(nn.Module):
             if any(p.requires_grad for p in m.parameters()):
                 return idx
         return None
-
-    def saved_activations(self) -> Dict[str, Tensor]:
-        """Test hook (read-only): what the last ``"hip"`` training forward stored, by name (the backbone's module lists
-        the names next to its ``_sequence``).  Valid while that forward's autograd graph is alive."""
-        return dict(self._train_state()["acts"])
 
     def stochastic_depth_factors(self) -> Dict[str, Tensor]:
         """Test hook (read-only): ``{branch name: factors [B]}`` (0 or 1 / (1 - p)) the last ``"hip"`` training forward
@@ -365,7 +164,7 @@ class HipBackbone(nn.Module):
         acts = state["acts"]
         if not acts:
             return {}
-        ops, _, grads, keep = self._backward_ops(acts, state["factors"], shape, cotangents, splits)
+        ops, _, grads, keep = self._backward_ops(acts, state.get("factors"), shape, cotangents, splits)
         if ops:
             self._run_plan(self.backward_struct, self.backward_prefix, ops, next(iter(acts.values())).device)
         return grads
@@ -382,19 +181,12 @@ class HipBackbone(nn.Module):
             raise RuntimeError(f"{who}: expected [B, 3, H, W], got {tuple(x.shape)}")
         return x
 
-    def _precision(self) -> int:
-        return 0 if self.compute_dtype == torch.float32 else 1
-
-    def _lib(self):
-        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
-
     def _packed(self, layer: nn.Module, layout: int = 0, scale: Union[None, float, Tensor] = None, scale_bias: bool = True,
                 pad_to: int = 1) -> Tuple[Tensor, Tensor]:
         """``(packed weight, bias)`` of a conv or Linear for the implicit GEMM (``sdetr_backbone_pack`` with a unit norm):
         ``scale`` (a layer scale, or a constant) folded into the weight and, with ``scale_bias``, the bias; a layer
         without a bias gets zeros; the output width zero-padded to a multiple of ``pad_to``.  Built once per parameter
         version, precision and compute dtype."""
-        precision, lib = self._precision(), self._lib()
         w = layer.weight
         co, ci, k = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
         cop = -(-co // pad_to) * pad_to
@@ -412,18 +204,11 @@ class HipBackbone(nn.Module):
             elif scale is not None:
                 gamma *= float(scale)
             beta = (b32 * gamma if scale_bias else b32).contiguous()
-            zeros, ones = torch.zeros(cop, device=dev), torch.ones(cop, device=dev)
-            nbytes = lib.sdetr_backbone_packed_bytes(cop, ci, k, precision)
-            packed = torch.empty(nbytes // 2, dtype=torch.int16, device=dev)
-            bias = torch.empty(cop, dtype=torch.float32, device=dev)
-            _hip.launch("sdetr_backbone_pack", lib, dev, w32.data_ptr(), gamma.data_ptr(), beta.data_ptr(), zeros.data_ptr(),
-                        ones.data_ptr(), 0.0, cop, ci, k, layout, precision, packed.data_ptr(), bias.data_ptr(),
-                        what=f"{type(self).__name__} (pack)")
-            return packed, bias
+            return self._pack(w32, (gamma, beta, torch.zeros(cop, device=dev), torch.ones(cop, device=dev)), 0.0, layout)
         sources = (w, layer.bias) + ((scale,) if isinstance(scale, Tensor) else ())
         fixed = None if isinstance(scale, Tensor) else scale
         return derived(layer, "rows_packed", sources, build,
-                       extra=(precision, self.compute_dtype, layout, fixed, scale_bias, pad_to))
+                       extra=(self._precision(), self.compute_dtype, layout, fixed, scale_bias, pad_to))
 
     def _affine(self, norm: nn.LayerNorm, scale: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """The LayerNorm's affine in fp32, a layer scale folded in: ``g * (w n + b) = (g w) n + g b``."""
@@ -438,7 +223,6 @@ class HipBackbone(nn.Module):
     def _packed_rows_dgrad(self, layer: nn.Module, scale: Optional[Tensor] = None) -> Tensor:
         """The backward-data planes (``sdetr_backbone_pack_dgrad``, kernel 1) of a Linear's ``[out, in]`` weight, ``scale``
         (the layer scale) folded per output; of the 2x2 down-sampler conv, its weight as ``[out, (ky, kx, in)]`` rows."""
-        precision, lib = self._precision(), self._lib()
         w = layer.weight
 
         def build():
@@ -446,27 +230,11 @@ class HipBackbone(nn.Module):
             if w32.dim() == 4:
                 w32 = w32.permute(0, 2, 3, 1)
             w32 = w32.reshape(w.shape[0], -1).contiguous()
-            co, ci = w32.shape
+            co = w32.shape[0]
             gamma = torch.ones(co, device=w.device) if scale is None else scale.detach().to(torch.float32).reshape(co).contiguous()
-            ones = torch.ones(co, device=w.device)
-            packed = torch.empty(lib.sdetr_backbone_dgrad_packed_bytes(co, ci, 1, precision) // 2, dtype=torch.int16,
-                                 device=w.device)
-            unused = torch.empty(co, dtype=torch.float32, device=w.device)
-            _hip.launch("sdetr_backbone_pack_dgrad", lib, w.device, w32.data_ptr(), gamma.data_ptr(), ones.data_ptr(), 0.0, co,
-                        ci, 1, precision, packed.data_ptr(), unused.data_ptr(), what=f"{type(self).__name__} (pack dgrad)")
-            return packed
-        return derived(layer, "rows_packed_dgrad", (w, scale), build, extra=(precision, self.compute_dtype))
+            return self._pack_dgrad(w32, gamma, torch.ones(co, device=w.device), 0.0)[0]
+        return derived(layer, "rows_packed_dgrad", (w, scale), build, extra=(self._precision(), self.compute_dtype))
 
     def _f32(self, owner, name: str, t: Tensor) -> Tensor:
         """A parameter as a contiguous fp32 tensor, cached per version."""
         return derived(owner, "rows_f32_" + name, (t,), lambda: t.detach().to(torch.float32).contiguous().clone())
-
-    def _run_plan(self, struct_type, c_prefix: str, ops: list, device) -> None:
-        """Launch ``ops`` in order: ``<c_prefix>_run`` over a workspace of ``<c_prefix>_workspace_bytes``."""
-        lib, precision, who = self._lib(), self._precision(), type(self).__name__
-        arr = (struct_type * len(ops))(*ops)
-        ws_bytes = getattr(lib, c_prefix + "_workspace_bytes")(arr, len(ops), precision)
-        if ws_bytes < 0:
-            _hip.check(-1, f"{who} (workspace)", lib)
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=device)
-        _hip.launch(c_prefix + "_run", lib, device, arr, len(ops), precision, ws.data_ptr(), ws_bytes, what=f"{who} (run)")

@@ -21,8 +21,8 @@ read fp32 / packed copies of them).  Anything else, and by default every call wi
 grad (training), takes the differentiable plain-torch composite on the device (``F.conv2d`` + ``F.group_norm``), the default
 autograd path of this row.  A CPU tensor on the HIP form raises: the hot path has no CPU fallback.
 
-Training in HIP (``set_train_form("hip")``, ``csrc/frontend_backward.hip``; the interface is the backbones'): a forward that
-needs autograd runs the same convolution launches and ``sdetr_frontend_groupnorm_train`` -- the inference GroupNorm, bit for
+Training in HIP (``set_train_form("hip")``, ``csrc/frontend_backward.hip``; the interface, its autograd node and the plan
+runner are ``hip_module.HipModule``'s, as the backbones' are): a forward that needs autograd runs the same convolution launches and ``sdetr_frontend_groupnorm_train`` -- the inference GroupNorm, bit for
 bit, which also keeps the raw convolution ``z`` and every group's (mean, rstd) -- inside ONE autograd node over the backbone
 maps and the trainable parameters.  Its backward is one ``sdetr_frontend_bwd_run`` plan (``build_backward_plan``), levels
 from the last to the first: the GroupNorm backward (from ``z`` and the statistics, never from the output: gamma may be
@@ -34,7 +34,6 @@ copy is what is stored and read; its gradient comes back dense, in the input's s
 (``hip_train_reason``), it never falls back.
 """
 import ctypes
-import weakref
 from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -42,8 +41,8 @@ import torch
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import BackwardPlanBuilder, _TrainState
 from .derived import derived
+from .hip_module import BackwardPlanBuilder, HipModule, _TrainFunction
 
 
 class _ConvNormActivation(nn.Sequential):
@@ -64,7 +63,7 @@ class _ConvNormActivation(nn.Sequential):
         self.out_channels = out_channels
 
 
-class ChannelMapper(nn.Module):
+class ChannelMapper(HipModule):
     def __init__(self, in_channels: List[int], out_channels: int, num_outs: int, kernel_size: int = 1, stride: int = 1,
                  groups: int = 1, norm_layer=partial(nn.GroupNorm, 32), activation_layer: nn.Module = None,
                  dilation: int = 1, inplace: bool = True, bias: bool = None):
@@ -93,14 +92,6 @@ class ChannelMapper(nn.Module):
                 if layer.bias is not None:
                     nn.init.constant_(layer.bias, 0)
 
-    def set_dtype(self, dtype: torch.dtype):
-        """Precision of the convolutions' products: ``torch.float32`` (fp32 accuracy), ``torch.bfloat16`` or
-        ``torch.float16`` (one 16-bit product, fp32 accumulation).  Parameters, statistics and output stay fp32."""
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError(f"ChannelMapper.set_dtype: {dtype} is not float32 / bfloat16 / float16")
-        self.compute_dtype = dtype
-        return self
-
     # ------------------------------------------------------------------------------------------ form checks
     def hip_form(self) -> bool:
         """True when the configuration is the one the HIP kernels serve (see the module docstring)."""
@@ -122,18 +113,13 @@ class ChannelMapper(nn.Module):
             return False   # a second extra level reads out_channels channels
         return len(self.convs) >= len(self.in_channels) and len(self.in_channels) < 8   # <= 8 levels per launch
 
-    def _needs_autograd(self, inputs: Sequence[Tensor]) -> bool:
-        if not torch.is_grad_enabled():
-            return False
-        return any(p.requires_grad for p in self.parameters()) or any(x.requires_grad for x in inputs)
-
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, inputs: Union[Dict[str, Tensor], Sequence[Tensor]]) -> List[Tensor]:
         inputs = list(inputs.values()) if isinstance(inputs, dict) else list(inputs)
         assert len(inputs) == len(self.in_channels)
-        if self.train_form == "hip" and self._needs_autograd(inputs):
+        if self.train_form == "hip" and self._needs_autograd(*inputs):
             return self.forward_hip_train(inputs)
-        if self._needs_autograd(inputs) or not self.hip_form():
+        if self._needs_autograd(*inputs) or not self.hip_form():
             return self.forward_torch(inputs)
         return self.forward_hip(inputs)
 
@@ -143,12 +129,6 @@ class ChannelMapper(nn.Module):
         for i in range(len(inputs), len(self.convs)):
             outs.append(self.convs[i](inputs[-1] if i == len(inputs) else outs[-1]))
         return outs
-
-    def _precision(self) -> int:
-        return 0 if self.compute_dtype == torch.float32 else 1
-
-    def _lib(self):
-        return _hip.lib(self.compute_dtype if self.compute_dtype == torch.float16 else None)
 
     def _packed_weight(self, i: int) -> Tensor:
         """Conv weight of level ``i`` packed for the kernel (``sdetr_frontend_pack_weight``: three bf16 planes of the exact
@@ -266,18 +246,7 @@ class ChannelMapper(nn.Module):
         return outs
 
     # ------------------------------------------------------------------------------------------ training in HIP
-    train_form = "torch"
-
-    def set_train_form(self, form: str):
-        """How a forward that needs autograd runs: ``"torch"`` (default: the composite ``forward_torch``) or ``"hip"``
-        (the HIP forward inside one autograd node whose backward is one ``sdetr_frontend_bwd_run`` plan, see
-        ``forward_hip_train``).  ``"hip"`` on a module or inputs that are not eligible (``hip_train_reason``) raises at
-        forward: it never falls back."""
-        if form not in ("torch", "hip"):
-            raise ValueError(f"ChannelMapper.set_train_form: {form!r} is not 'torch' / 'hip'")
-        self.train_form = form
-        return self
-
+    # (the interface is HipModule's; the backward of the node is one ``sdetr_frontend_bwd_run`` plan)
     def hip_train_reason(self, inputs: Optional[Sequence[Tensor]] = None) -> Optional[str]:
         """Why the ``"hip"`` training form cannot serve this module (and ``inputs``); ``None`` when it can."""
         if not self.hip_form():
@@ -291,49 +260,30 @@ class ChannelMapper(nn.Module):
             return "an input is a CPU tensor: the hot path has no CPU fallback"
         return None
 
-    def hip_train_form(self, inputs: Optional[Sequence[Tensor]] = None) -> bool:
-        """True when ``set_train_form("hip")`` can train this module (on ``inputs``)."""
-        return self.hip_train_reason(inputs) is None
-
     def forward_hip_train(self, inputs: Sequence[Tensor], splits: int = 0) -> List[Tensor]:
         """The ``"hip"`` training form: ``forward_hip`` with the training GroupNorm as one autograd node over the inputs
         and the trainable parameters.  The node keeps the raw convolutions ``z``, the (mean, rstd) of every group and the
         inputs (no copy); its backward is one plan and returns fp32 gradients, which autograd accumulates."""
         inputs = list(inputs.values()) if isinstance(inputs, dict) else list(inputs)
-        reason = self.hip_train_reason(inputs)
-        if reason is not None:
-            raise RuntimeError(f"ChannelMapper: the 'hip' training form cannot run: {reason}")
+        self._check_train_form(inputs)
         named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
-        return list(_MapperTrainFunction.apply(self, len(inputs), splits, tuple(n for n, _ in named), *inputs,
-                                               *[p for _, p in named]))
+        return list(_TrainFunction.apply(self, len(inputs), splits, tuple(n for n, _ in named), *inputs, *[p for _, p in named]))
 
-    def saved_activations(self) -> Dict[str, Tensor]:
-        """Test hook (read-only): what the last ``"hip"`` training forward stored, by the names of ``build_plan``.  Valid
-        while that forward's autograd graph is alive."""
-        state = self.__dict__.get("_train_state_ref")
-        state = state() if state is not None else None
-        if state is None:
-            raise RuntimeError("ChannelMapper: no 'hip' training forward is alive")
-        return dict(state["acts"])
+    def _train_forward(self, inputs: Sequence[Tensor], splits: int, state: dict) -> Tuple[Tensor, ...]:
+        """(The stored names are ``build_plan``'s.)"""
+        return tuple(self.forward_hip(inputs, state))
 
     def _packed_dgrad(self, i: int) -> Tensor:
         """The backward-data planes of level ``i``'s conv weight (``sdetr_backbone_pack_dgrad`` with a unit scale), built
         once per parameter version and precision."""
         conv = self.convs[i][0]
         w = conv.weight
-        precision, lib = self._precision(), self._lib()
 
         def build():
-            co, ci, k = w.shape[0], w.shape[1], w.shape[2]
             w32 = w.detach().to(torch.float32).contiguous()
-            ones = torch.ones(co, device=w.device)
-            packed = torch.empty(lib.sdetr_backbone_dgrad_packed_bytes(co, ci, k, precision) // 2, dtype=torch.int16,
-                                 device=w.device)
-            unused = torch.empty(co, dtype=torch.float32, device=w.device)
-            _hip.launch("sdetr_backbone_pack_dgrad", lib, w.device, w32.data_ptr(), ones.data_ptr(), ones.data_ptr(), 0.0, co,
-                        ci, k, precision, packed.data_ptr(), unused.data_ptr(), what="ChannelMapper (pack dgrad)")
-            return packed
-        return derived(conv, "frontend_packed_dgrad", (w,), build, extra=(precision, self.compute_dtype))
+            ones = torch.ones(w.shape[0], device=w.device)
+            return self._pack_dgrad(w32, ones, ones, 0.0)[0]
+        return derived(conv, "frontend_packed_dgrad", (w,), build, extra=(self._precision(), self.compute_dtype))
 
     def build_backward_plan(self, acts: Dict[str, Tensor], cotangents: Sequence[Optional[Tensor]],
                             input_grads: Sequence[bool], splits: int = 0):
@@ -412,33 +362,7 @@ class ChannelMapper(nn.Module):
         """Runs the backward plan on what the forward stored: ``({parameter name: fp32 gradient}, input gradients)``."""
         ops, _, grads, dxs, keep = self.build_backward_plan(state["acts"], cotangents, input_grads, splits)
         if ops:
-            lib, precision = self._lib(), self._precision()
-            arr = (_hip.FrontendBwdOpStruct * len(ops))(*ops)
-            ws_bytes = lib.sdetr_frontend_bwd_workspace_bytes(arr, len(ops), precision)
-            if ws_bytes < 0:
-                _hip.check(-1, "ChannelMapper (backward workspace)", lib)
-            dev = keep[0].device
-            ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
-            _hip.launch("sdetr_frontend_bwd_run", lib, dev, arr, len(ops), precision, ws.data_ptr(), ws_bytes,
-                        what="ChannelMapper (backward)")
+            self._run_plan(_hip.FrontendBwdOpStruct, "sdetr_frontend_bwd", ops, keep[0].device)
         return grads, dxs
 
-
-class _MapperTrainFunction(torch.autograd.Function):
-    """``ChannelMapper.forward_hip_train``: inputs are the backbone maps and the trainable parameters, outputs the
-    levels' fp32 NCHW maps."""
-
-    @staticmethod
-    def forward(ctx, mapper: ChannelMapper, n_inputs: int, splits: int, names: Tuple[str, ...], *tensors: Tensor):
-        state = _TrainState()
-        outs = mapper.forward_hip(tensors[:n_inputs], state)
-        ctx.mapper, ctx.state, ctx.names, ctx.splits, ctx.n_inputs = mapper, state, names, splits, n_inputs
-        mapper.__dict__["_train_state_ref"] = weakref.ref(state)
-        return tuple(outs)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *cotangents):
-        wanted = ctx.needs_input_grad[4:4 + ctx.n_inputs]
-        grads, dxs = ctx.mapper._run_backward(ctx.state, cotangents, wanted, ctx.splits)
-        return (None, None, None, None) + tuple(dxs) + tuple(grads.get(n) for n in ctx.names)
+    _train_backward = _run_backward   # the autograd node's hook takes exactly these

@@ -42,9 +42,10 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import BackwardPlanBuilder, HipBackbone, PlanBuilder
+from .backbone_base import HipBackbone
 from .backbone_base import Permute, StochasticDepth  # noqa: F401 (both modules re-exported)
 from .derived import derived
+from .hip_module import BackwardPlanBuilder, PlanBuilder
 
 
 class LayerNorm2d(nn.LayerNorm):

@@ -34,8 +34,9 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import HipBackbone, PlanBuilder, StochasticDepth
+from .backbone_base import HipBackbone, StochasticDepth
 from .derived import derived
+from .hip_module import PlanBuilder
 
 MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/backbone_rows_core.h)
 FOCAL_KERNELS = (3, 5, 7, 9)

@@ -48,8 +48,9 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _hip
-from .backbone_base import BackwardPlanBuilder, HipBackbone, Permute, PlanBuilder, StochasticDepth
+from .backbone_base import HipBackbone, Permute, StochasticDepth
 from .derived import derived
+from .hip_module import BackwardPlanBuilder, PlanBuilder
 
 MAX_CHANNELS = 3072          # a LayerNorm row in registers (csrc/backbone_rows_core.h); the merging norm sees 4 C
 WINDOWS = (7, 12)

@@ -1,19 +1,23 @@
-"""CPU: what the four backbones take from ``HipBackbone`` since the training interface moved there: the interface is
-the base's own, a backbone that cannot serve the ``"hip"`` form refuses it with a reason instead of running something
+"""CPU: what the four backbones take from ``HipBackbone`` and, with the ChannelMapper, from ``HipModule`` below it, since
+the training interface moved there: the interface is the base's own, one autograd node serves every module, a backbone that cannot serve the ``"hip"`` form refuses it with a reason instead of running something
 else, the ResNet loads checkpoints through the base's ``load_weights``, and the ConvNeXt and Swin backward plans come
 from the base's ``BackwardPlanBuilder``."""
+import ast
 import ctypes
+import os
 
 import pytest
 import torch
 
 import convnext_train_cases as CT
 import swin_train_cases as ST
-from salience_detr_amd import _hip
+from salience_detr_amd import _hip, hip_module
 from salience_detr_amd.backbone import ResNetBackbone
 from salience_detr_amd.backbone_base import HipBackbone
+from salience_detr_amd.channel_mapper import ChannelMapper
 from salience_detr_amd.convnext import CNBlockConfig, ConvNeXtBackbone
 from salience_detr_amd.focalnet import FocalNetBackbone
+from salience_detr_amd.hip_module import HipModule
 from salience_detr_amd.swin import SwinBackbone
 
 SHARED = ("set_train_form", "hip_train_reason", "hip_train_form", "forward", "forward_hip_train", "_train_state",
@@ -25,6 +29,31 @@ def test_the_training_interface_is_the_base_class_s(cls):
     for name in SHARED:
         assert getattr(cls, name) is getattr(HipBackbone, name), name
     assert "train_form" not in cls.__dict__ and HipBackbone.train_form == "torch"
+
+
+MODULE_SHARED = ("set_dtype", "set_train_form", "hip_train_form", "_train_state", "_run_plan", "_precision", "_lib")
+
+
+def test_the_channel_mapper_takes_the_interface_from_hip_module_as_the_backbones_do():
+    for name in MODULE_SHARED:
+        assert getattr(ChannelMapper, name) is getattr(HipModule, name), name
+        assert getattr(HipBackbone, name) is getattr(HipModule, name), name
+    assert "train_form" not in ChannelMapper.__dict__ and HipModule.train_form == "torch"
+    assert ResNetBackbone._run_backward is HipBackbone._run_backward
+    assert ResNetBackbone.backward_struct is _hip.BackboneBwdOpStruct and ResNetBackbone.backward_prefix == "sdetr_backbone_bwd"
+
+
+def test_one_autograd_node_serves_every_forward_hip_train():
+    """Source level: the modules with a ``forward_hip_train`` define one ``torch.autograd.Function`` subclass between them."""
+    files = ("hip_module", "backbone_base", "channel_mapper", "backbone", "convnext", "focalnet", "swin")
+    found = []
+    for name in files:
+        with open(os.path.join(os.path.dirname(hip_module.__file__), name + ".py")) as f:
+            tree = ast.parse(f.read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ClassDef) and any(ast.unparse(b).endswith("autograd.Function") for b in node.bases):
+                found.append(f"{name}.{node.name}")
+    assert found == ["hip_module._TrainFunction"]
 
 
 def _focalnet():
