@@ -1332,6 +1332,21 @@ int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, i
  * as sdetr_backbone_batch_images does, with canvas and mask as described there and every element of both written by the
  * launch; the resized sizes must fit the canvas.  Equal, bit for bit, to sdetr_backbone_batch_images on the outputs of
  * sdetr_backbone_resize_images.
+ *
+ * The training transform (transforms/presets.py detr / multiscale / hflip on tensors), csrc/train_transform.hip:
+ * sdetr_backbone_train_batch_images is horizontal flip -> resize -> crop -> resize -> (u8: / 255) -> normalise -> pad +
+ * mask in ONE launch, every value from the routine of the two launches above.  plan = host int [batch][10] per image:
+ * flip (0; 1: the source is read mirrored along the width; 2: the result of a plan with at most one resize is mirrored),
+ * n_stages (0: no resize, the final size is the image's; 1: one resize to the final size; 2: resize to (h1, w1), crop,
+ * resize to the final size), h1, w1, crop top, left, height, width (read with n_stages 2 only; the crop must lie inside
+ * h1 x w1), final nh, nw (must fit the canvas).  u8 values are rounded half to even after EVERY resize, as the
+ * reference's cast round trip.  canvas and mask as sdetr_backbone_batch_images, every element of both written.  Equal,
+ * bit for bit, to sdetr_backbone_batch_images of the images built step by step (mirror, sdetr_backbone_resize_images,
+ * slice, sdetr_backbone_resize_images).  The intermediate image is never in memory: a workgroup stages the window of it
+ * that its 64 x 4 output tile reads (12 x 96 pixels: any second resize that shrinks by up to 1.25), and recomputes the
+ * intermediate pixels tap by tap where the window is larger (any factor runs).  Sides 1 .. 2^24, at most 64 images.
+ * sdetr_backbone_train_plan_stats (host arithmetic, no launch): over the images with n_stages 2, the number of
+ * workgroups that stage their window and the number that recompute.
  * --------------------------------------------------------------------------------------------- */
 typedef struct sdetr_backbone_op {
     int op;
@@ -1376,6 +1391,11 @@ int sdetr_backbone_resize_images(sdetr_stream_t stream, const void *const *image
 int sdetr_backbone_resize_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw,
                                        const int *out_hw, int batch, int is_uint8, int canvas_height, int canvas_width,
                                        float *canvas, uint8_t *mask);
+int sdetr_backbone_train_batch_images(sdetr_stream_t stream, const void *const *images, const int *image_hw,
+                                      const int *plan, int batch, int is_uint8, int canvas_height, int canvas_width,
+                                      float *canvas, uint8_t *mask);
+int sdetr_backbone_train_plan_stats(const int *image_hw, const int *plan, int batch, int64_t *staged,
+                                    int64_t *recomputed);
 
 /* ---------------------------------------------------------------------------------------------
  * Backbone backward (training the ResNet, csrc/backbone_backward.hip): the gradients of the conv ops above, for

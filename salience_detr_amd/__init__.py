@@ -4,7 +4,9 @@ points are also reachable from the package, resolved on first use so that import
 _LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "SalienceDETRHead": "detector",
          "EvalResize": "eval_resize", "eval_resize_size": "eval_resize", "batch_images": "backbone",
          "ConvNeXtBackbone": "convnext", "CNBlockConfig": "convnext", "FocalNetBackbone": "focalnet",
-         "SwinBackbone": "swin"}
+         "SwinBackbone": "swin", "TrainTransform": "train_transform", "TrainBatch": "train_transform",
+         "AugmentParams": "train_transform", "sample_params": "train_transform", "shortest_size": "train_transform",
+         "transform_targets": "train_transform"}
 
 
 def __getattr__(name):

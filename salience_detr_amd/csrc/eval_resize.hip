@@ -7,7 +7,7 @@
 // what handles the borders).  The horizontal sum of every tap row is taken first, then the vertical sum of those, as the
 // framework's two passes do.
 //
-// Two launches share resized_pixel(), the ONE routine for a pixel's value:
+// Two launches share resized_pixel() (resize_core.h, also the training transform's), the ONE routine for a pixel's value:
 //   * eval_resize_kernel<T, false>: [3, h, w] -> tightly packed [3, nh, nw] of the same type (u8: round half to even);
 //   * eval_resize_kernel<T, true>: the same value (+ for u8 that rounding, then / 255) -> Normalize -> the zero-padded
 //     canvas and the padding mask of sdetr_backbone_batch_images_ex, every element written by this launch.
@@ -20,13 +20,10 @@
 
 #include "common.h"
 #include "image_norm.h"
+#include "resize_core.h"
 
 namespace sdetr {
 namespace {
-
-constexpr int kRMaxImages = 64;
-constexpr int kRTileW = 64, kRTileH = 4;
-constexpr int kRMaxSide = 1 << 24;   // tap indices are exact in fp32 up to here
 
 struct ResizeArgs {
     const void *img[kRMaxImages];
@@ -36,77 +33,6 @@ struct ResizeArgs {
     float *canvas;
     uint8_t *mask;
 };
-
-struct AxisTap {
-    int lo, n;
-    float center, norm, invscale;
-};
-
-__device__ __forceinline__ float triangle(float x)
-{
-    x = fabsf(x);
-    return x < 1.f ? 1.f - x : 0.f;
-}
-
-// un-normalised weight of tap j of an entry
-__device__ __forceinline__ float raw_weight(const AxisTap &t, int j)
-{
-    return triangle(((float)(t.lo + j) - t.center + 0.5f) * t.invscale);
-}
-
-__device__ __forceinline__ float tap_weight(const AxisTap &t, int j) { return raw_weight(t, j) * t.norm; }
-
-// the window of output index i on an axis of `in` -> `out` samples
-__device__ AxisTap axis_tap(int i, int in, int out)
-{
-    const float scale = (float)in / (float)out;
-    const float support = scale >= 1.f ? scale : 1.f;
-    AxisTap t;
-    t.invscale = scale >= 1.f ? 1.f / scale : 1.f;
-    t.center = scale * ((float)i + 0.5f);
-    // (the half is added in double and truncated, as the framework does)
-    const int max_taps = (int)ceilf(support) * 2 + 1;
-    t.lo = max((int)((double)(t.center - support) + 0.5), 0);
-    t.n = min(max(min((int)((double)(t.center + support) + 0.5), in) - t.lo, 0), max_taps);
-    float total = 0.f;
-    for (int j = 0; j < t.n; ++j) total += raw_weight(t, j);
-    t.norm = total != 0.f ? 1.f / total : 1.f;
-    return t;
-}
-
-template <typename T>
-__device__ __forceinline__ float pixel_as_float(T v) { return (float)v; }
-
-// The resized value of the three channels of one output pixel, as a float of the image's own type: for u8 the sum over
-// the 0..255 values rounded half to even (torch.round + the cast back).  Zero-weight taps are skipped, so an output
-// whose size equals the input's is the input bit for bit.
-template <typename T>
-__device__ __forceinline__ void resized_pixel(const T *img, int h, int w, const AxisTap &ty, const AxisTap &tx, float v[3])
-{
-    const int64_t plane = (int64_t)h * w;
-    float acc[3] = {0.f, 0.f, 0.f};
-    bool first_row = true;
-    for (int j = 0; j < ty.n; ++j) {
-        const float wy = tap_weight(ty, j);
-        if (wy == 0.f) continue;
-        const T *row = img + (int64_t)(ty.lo + j) * w + tx.lo;
-        float t[3] = {0.f, 0.f, 0.f};
-        bool first = true;
-        for (int i = 0; i < tx.n; ++i) {
-            const float wx = tap_weight(tx, i);
-            if (wx == 0.f) continue;
-            for (int ch = 0; ch < 3; ++ch) {
-                const float s = pixel_as_float(row[ch * plane + i]);
-                t[ch] = first ? __fmul_rn(s, wx) : fmaf(s, wx, t[ch]);
-            }
-            first = false;
-        }
-        for (int ch = 0; ch < 3; ++ch) acc[ch] = first_row ? __fmul_rn(t[ch], wy) : fmaf(t[ch], wy, acc[ch]);
-        first_row = false;
-    }
-    for (int ch = 0; ch < 3; ++ch)
-        v[ch] = std::is_same<T, uint8_t>::value ? fminf(fmaxf(rintf(acc[ch]), 0.f), 255.f) : acc[ch];
-}
 
 template <typename T, bool FUSED>
 __global__ void __launch_bounds__(kRTileW * kRTileH) eval_resize_kernel(ResizeArgs a)
@@ -131,7 +57,7 @@ __global__ void __launch_bounds__(kRTileW * kRTileH) eval_resize_kernel(ResizeAr
     const int oy = y0 + ly, ox = x0 + lx;
     const bool in = oy < nh && ox < nw;
     float v[3] = {0.f, 0.f, 0.f};
-    if (in) resized_pixel(reinterpret_cast<const T *>(a.img[b]), h, w, s_y[ly], s_x[lx], v);
+    if (in) resized_pixel<std::is_same<T, uint8_t>::value>(planar_source<T>(a.img[b], h, w, false), s_y[ly], s_x[lx], v);
     if (FUSED) {
         if (oy >= a.hp || ox >= a.wp) return;
         const int64_t plane = (int64_t)a.hp * a.wp, p = (int64_t)oy * a.wp + ox;

@@ -30,7 +30,9 @@ generator (``denoising.GenerateCDNQueries``, held as ``denoising_generator`` so 
 ``_classes_`` removed: ``train_state_dict``), the set criterion, the denoising loss and -- as absolute boxes -- the
 salience criterion.  The first ``n_dn`` queries of every decoder layer are split off as the denoising output
 (``dn_post_process``); the result is ``{k: loss[k] * weight_dict[k]}`` as in the reference.  A detector built without
-``criterion`` has exactly the module tree and state-dict keys of the eval detector.
+``criterion`` has exactly the module tree and state-dict keys of the eval detector.  ``forward_batch(batch)`` is the same
+training forward from the canvas ``train_transform.TrainTransform`` builds out of decoded images (the dataset transform
+in one launch), without batching the images again.
 """
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -275,6 +277,25 @@ class SalienceDETR(SalienceDETRHead):
             return self.forward_train(self.backbone(canvas), mask, prepared, sizes, tuple(canvas.shape[-2:]), noise=noise)
         with torch.no_grad():
             return self._detect_images(images, sizes)
+
+    def forward_batch(self, batch, noise=None) -> Dict[str, Tensor]:
+        """The training forward from a ready canvas: ``batch`` is ``train_transform.TrainBatch`` (``TrainTransform``'s
+        result: the normalised padded canvas, the padding mask, the transformed image sizes and targets), so the images
+        are not batched again: ``prepare_targets`` -> backbone -> ``forward_train``.  Returns the weighted loss dict, the
+        one ``forward(images, targets)`` gives for the images inside the canvas.  Training only: a detector built
+        without ``criterion``, eval mode and a batch without targets raise."""
+        if self.criterion is None:
+            raise RuntimeError(f"{type(self).__name__}: built without a criterion; there is no training forward")
+        if not self.training:
+            raise RuntimeError(f"{type(self).__name__}: forward_batch is the training forward; call train() first "
+                               "(eval() detections come from forward(images))")
+        self._wants_training(batch.targets)
+        sizes = tuple((int(h), int(w)) for h, w in batch.image_sizes)
+        if len(batch.targets) != len(sizes) or batch.canvas.shape[0] != len(sizes):
+            raise RuntimeError("SalienceDETR: one target dict per image expected")
+        prepared = prepare_targets(batch.targets, sizes)
+        return self.forward_train(self.backbone(batch.canvas), batch.mask, prepared, sizes,
+                                  tuple(batch.canvas.shape[-2:]), noise=noise)
 
     def _detect_images(self, images, sizes) -> List[Dict[str, Tensor]]:
         key = (sizes, images[0].device)
