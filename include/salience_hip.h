@@ -1922,6 +1922,59 @@ int sdetr_adamw_clip_step(sdetr_stream_t stream, const sdetr_adamw_record *recor
                           int num_groups, float *exp_avg, float *exp_avg_sq, double beta1, double beta2, double eps,
                           float max_norm, float grad_scale, float *total_norm);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO box evaluation (reference util/engine.py:evaluate_acc -> util/coco_eval.py -> pycocotools COCOeval, iouType
+ * "bbox", default parameters), csrc/coco_eval.hip.  10 IoU thresholds, 101 recall thresholds, maxDets 1 / 10 / 100, area
+ * ranges all / small / medium / large (bit index of a (area, threshold) pair: area * 10 + threshold).
+ *
+ * Records are rows of int64 words.
+ *   detection record, SDETR_COCO_DET_WORDS words: image id | category index (low 32 bits) + rank within its (image,
+ *     category) (high 32) | the score as the bits of a double | matched bits (40) | ignored bits (40).
+ *   ground-truth record, SDETR_COCO_GT_WORDS words, one per (image, category that has ground truths): image id |
+ *     category index | non-ignored ground truths in the four area ranges (-1 in all four: more than SDETR_COCO_GT_CAP
+ *     ground truths in this (image, category); the evaluator raises) | ground truths, crowds included.
+ *   A padding row has -1 in its first two words.
+ *
+ * sdetr_coco_eval_update: ONE launch per batch, one workgroup per image.  scores fp32 [batch, k], labels int64
+ * [batch, k], boxes fp32 [batch, k, 4] (x1, y1, x2, y2) pixels, count int32 [batch] (what detections_padded returns,
+ * scores widened); gt_boxes fp32 [batch, max_gt, 4] xyxy pixels, gt_labels int64, gt_area f64, gt_crowd uint8
+ * [batch, max_gt], gt_count int32 [batch], image_ids int64 [batch].  category_lut int32 [lut_size]: label -> index into
+ * the sorted category ids, -1 for a label that is no category (dropped).  iou_thresholds f64 [10].  Writes every row
+ * of det_records [batch * k, 5] and gt_records [batch * max_gt, 7] (real rows first, image by image, positions from a
+ * prefix over the batch's images; padding behind) and totals int32 [2] = real detection rows, real ground-truth rows.
+ * No atomics on global memory, no host sync: the same inputs give the same bytes, under graph replay too.
+ * Limits: k <= SDETR_COCO_MAX_DET_PER_IMAGE, max_gt <= SDETR_COCO_MAX_GT_PER_IMAGE, num_categories <=
+ * SDETR_COCO_MAX_CATEGORIES, at most SDETR_COCO_GT_CAP ground truths per (image, category).
+ *
+ * sdetr_coco_eval_accumulate: one workgroup per (category, area, maxDet) over records sorted by category, then by
+ * descending score (ties: ascending image id, then rank).  category_first int64 [K + 1]: rows of category c are
+ * [category_first[c], category_first[c + 1]).  npig int64 [K, 4].  recall_thresholds f64 [101], non-decreasing.
+ * Writes precision and scores f64 [10, 101, K, 4, 3] and recall f64 [10, K, 4, 3] (every element).  A category of any
+ * length is streamed in chunks of SDETR_COCO_ACC_CHUNK records with the scans carried across chunks.
+ * --------------------------------------------------------------------------------------------- */
+#define SDETR_COCO_THRESHOLDS 10
+#define SDETR_COCO_RECALL_POINTS 101
+#define SDETR_COCO_AREAS 4
+#define SDETR_COCO_MAX_DETS 100
+#define SDETR_COCO_DET_WORDS 5
+#define SDETR_COCO_GT_WORDS 7
+#define SDETR_COCO_MAX_CATEGORIES 2048
+#define SDETR_COCO_MAX_DET_PER_IMAGE 1024
+#define SDETR_COCO_MAX_GT_PER_IMAGE 1024
+#define SDETR_COCO_GT_CAP 128
+#define SDETR_COCO_ACC_CHUNK 1024
+
+int sdetr_coco_eval_gt_capacity(void);
+int sdetr_coco_eval_chunk_records(void);
+int sdetr_coco_eval_update(sdetr_stream_t stream, const float *scores, const int64_t *labels, const float *boxes,
+                           const int *count, int batch, int k, const float *gt_boxes, const int64_t *gt_labels,
+                           const double *gt_area, const uint8_t *gt_crowd, const int *gt_count, const int64_t *image_ids,
+                           int max_gt, const int *category_lut, int lut_size, int num_categories,
+                           const double *iou_thresholds, int64_t *det_records, int64_t *gt_records, int *totals);
+int sdetr_coco_eval_accumulate(sdetr_stream_t stream, const int64_t *records, int64_t num_records,
+                               const int64_t *category_first, const int64_t *npig, int num_categories,
+                               const double *recall_thresholds, double *precision, double *recall, double *scores);
+
 #ifdef __cplusplus
 }
 #endif

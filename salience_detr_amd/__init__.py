@@ -6,7 +6,7 @@ _LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "Salienc
          "ConvNeXtBackbone": "convnext", "CNBlockConfig": "convnext", "FocalNetBackbone": "focalnet",
          "SwinBackbone": "swin", "TrainTransform": "train_transform", "TrainBatch": "train_transform",
          "AugmentParams": "train_transform", "sample_params": "train_transform", "shortest_size": "train_transform",
-         "transform_targets": "train_transform"}
+         "transform_targets": "train_transform", "CocoBoxEvaluator": "coco_eval", "evaluate": "coco_eval"}
 
 
 def __getattr__(name):
