@@ -1156,6 +1156,31 @@ int sdetr_attention_train_backward_f32(sdetr_stream_t stream, const float *q, in
                                        const float *grad_out, float *grad_q, float *grad_k, float *grad_v);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same attention at ANY row count with an optional boolean mask (models/bricks/salience_transformer.py:566-573: the
+ * decoder layer's self-attention over its matching + denoising queries under the denoising mask).  Operands, layouts and
+ * outputs as sdetr_attention_train_*_f32 above.  mask: NULL, or [num_rows, num_rows] bytes (torch.bool storage), byte
+ * (i, j) at mask + i * mask_row_stride + j (mask_row_stride >= num_rows), row = query, column = key, non-zero = the query
+ * may NOT attend to the key; shared by all images and heads.  A masked pair is skipped (no arithmetic on -inf).  A fully
+ * masked row -- NaN in torch -- is defined: its out row is 0, its lse is 0, and it contributes 0 to every gradient;
+ * nothing is NaN or Inf for finite inputs.  Keys (forward, grad_q) and query rows (grad_k, grad_v) are walked in LDS tiles
+ * of sdetr_attention_train_masked_tile_rows() rows.  Every output element is written exactly once; no workspace, no
+ * allocation, no synchronisation (three launches that replay inside a captured graph).  num_rows == 0 or batch_size == 0:
+ * returns 0 without a launch.
+ * --------------------------------------------------------------------------------------------- */
+int sdetr_attention_train_masked_tile_rows(void);
+int sdetr_attention_train_masked_forward_f32(sdetr_stream_t stream, const float *q, int64_t q_batch_stride, int64_t q_row_stride,
+                                             const float *k, int64_t k_batch_stride, int64_t k_row_stride, const float *v,
+                                             int64_t v_batch_stride, int64_t v_row_stride, int batch_size, int num_heads,
+                                             int num_rows, int head_dim, float scale, const uint8_t *mask,
+                                             int64_t mask_row_stride, float *out, float *lse);
+int sdetr_attention_train_masked_backward_f32(sdetr_stream_t stream, const float *q, int64_t q_batch_stride, int64_t q_row_stride,
+                                              const float *k, int64_t k_batch_stride, int64_t k_row_stride, const float *v,
+                                              int64_t v_batch_stride, int64_t v_row_stride, int batch_size, int num_heads,
+                                              int num_rows, int head_dim, float scale, const uint8_t *mask,
+                                              int64_t mask_row_stride, const float *out, const float *lse,
+                                              const float *grad_out, float *grad_q, float *grad_k, float *grad_v);
+
+/* ---------------------------------------------------------------------------------------------
  * Detector input stage (row N7): ChannelMapper (models/necks/channel_mapper.py) convolutions + GroupNorm, per-level
  * padding masks and sine positions (models/bricks/position_encoding.py:9-67, salience_detr.py:172-176).
  *

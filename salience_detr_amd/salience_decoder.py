@@ -12,7 +12,9 @@ this decoder unchanged.  The no-grad path is arranged for the hardware like the 
 * residual adds + LayerNorms are single launches; the feed-forward block uses the one-launch MFMA kernel when the
   query count is large enough, library GEMMs otherwise (900 queries per image are not).
 
-With autograd enabled every layer runs plain differentiable torch ops around the HIP forward/backward op.
+With autograd enabled every layer runs plain differentiable torch ops around the HIP forward/backward op; after
+``SalienceTransformerDecoder.set_train_form("hip")`` the layers' masked self-attention is the native training kernel too
+(``csrc/attention_train_masked.hip``).
 """
 import copy
 import math
@@ -22,6 +24,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
+from . import attention_train
 from .filter_ops import (attention_heads, attention_heads_applies, box_refine, decoder_head, decoder_head_applies,
                          decoder_query_sine_embed, fused_ffn,
                          fused_ffn_applies, fused_layer_norm, mlp_rows, mlp_rows_applies, ref_point_head,
@@ -95,6 +98,9 @@ class SalienceTransformerDecoderLayer(nn.Module):
     """Self-attention over the queries, deformable cross-attention into ``memory``, feed-forward
     (salience_transformer.py:500-588); note the module order norm2 / norm1 / norm3 of the reference."""
 
+    # how the autograd branch computes the self-attention: set through SalienceTransformerDecoder.set_train_form
+    train_form = "torch"
+
     def __init__(self, embed_dim=256, d_ffn=1024, n_heads=8, dropout=0.1, activation=nn.ReLU(inplace=True), n_levels=4,
                  n_points=4):
         super().__init__()
@@ -130,6 +136,25 @@ class SalienceTransformerDecoderLayer(nn.Module):
 
     def _self_attention(self, qk: Tensor, v: Tensor, attn_mask: Optional[Tensor]) -> Tensor:
         return self.self_attn(query=qk, key=qk, value=v, attn_mask=attn_mask, need_weights=False)[0]
+
+    def _self_attention_train(self, query: Tensor, query_pos: Optional[Tensor], attn_mask: Optional[Tensor]) -> Tensor:
+        """The autograd branch's self-attention.  ``train_form == "torch"`` (default): ``nn.MultiheadAttention``.
+        ``"hip"``: the q | k and the v projections as two GEMMs on their own rows, the attention core under the boolean
+        mask as one launch forward, two backward (``attention_train.attention_qk_v_masked``: no head-split copies, no
+        additive [Nq, Nq] mask), then the out-projection -- for fp32 HIP rows with 32-channel heads, a ``torch.bool``
+        [Nq, Nq] mask or none, and no active attention dropout; anything else takes the module, as ``"torch"`` does."""
+        mha = self.self_attn
+        if (self.train_form == "hip" and torch.is_grad_enabled() and query.is_cuda and query.dtype == torch.float32
+                and not torch.is_autocast_enabled() and not (self.training and mha.dropout > 0.0)
+                and mha.in_proj_weight is not None and mha.in_proj_bias is not None):
+            E = query.shape[-1]
+            w, b = mha.in_proj_weight, mha.in_proj_bias
+            qk = F.linear(self.with_pos_embed(query, query_pos), w[:2 * E], b[:2 * E])
+            v = F.linear(query, w[2 * E:], b[2 * E:])
+            if attention_train.applies_masked(qk, v, mha.num_heads, attn_mask):
+                heads = attention_train.attention_qk_v_masked(qk, v, mha.num_heads, attn_mask)
+                return F.linear(heads, mha.out_proj.weight, mha.out_proj.bias)
+        return self._self_attention(self.with_pos_embed(query, query_pos), query, attn_mask)
 
     def _self_attention_native(self, query: Tensor, query_pos: Tensor, attn_mask: Optional[Tensor], project: bool = True):
         """nn.MultiheadAttention(q = k = query + pos, v = query) on its parameters without the module's layout copies:
@@ -175,7 +200,7 @@ class SalienceTransformerDecoderLayer(nn.Module):
                 query = rows_linear_ln(query2, self.self_attn.out_proj, self.norm2, residual=query)
                 query2 = None
         else:
-            query2 = self._self_attention(self.with_pos_embed(query, query_pos), query, self_attn_mask)
+            query2 = self._self_attention_train(query, query_pos, self_attn_mask)
         if not native:
             query = add_layer_norm(query, self.norm2, self.dropout2(query2))
             query2 = self.cross_attn(query=self.with_pos_embed(query, query_pos), reference_points=reference_points,
@@ -215,7 +240,21 @@ class SalienceTransformerDecoder(nn.Module):
         self.class_head = nn.ModuleList([nn.Linear(self.embed_dim, num_classes) for _ in range(num_layers)])
         self.bbox_head = nn.ModuleList([MLP(self.embed_dim, self.embed_dim, 4, 3) for _ in range(num_layers)])
         self.norm = nn.LayerNorm(self.embed_dim)
+        self.train_form = "torch"
         self.init_weights()
+
+    def set_train_form(self, form: str):
+        """How the layers' self-attention runs when a forward needs autograd: ``"torch"`` (default:
+        ``nn.MultiheadAttention``) or ``"hip"`` (``attention_train.attention_qk_v_masked`` between two projection GEMMs
+        and the out-projection, see ``SalienceTransformerDecoderLayer._self_attention_train``; what that kernel does not
+        serve -- 16-bit rows, a float or per-head mask, active attention dropout -- still takes the module).  The no-grad
+        path does not look at it."""
+        if form not in ("torch", "hip"):
+            raise ValueError(f"{type(self).__name__}.set_train_form: {form!r} is not 'torch' / 'hip'")
+        self.train_form = form
+        for layer in self.layers:
+            layer.train_form = form
+        return self
 
     def init_weights(self):
         for layer in self.layers:
