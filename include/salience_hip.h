@@ -894,6 +894,109 @@ int sdetr_neck_gate_shortcut(sdetr_stream_t stream, const void *y, int dtype, in
                              int hidden, const void *shortcut, int shortcut_row_stride, const void *shortcut2,
                              int shortcut2_row_stride, void *workspace, int64_t workspace_bytes, float *gate, void *out);
 
+/* ---- (13b) training the RepVGGPluX neck (csrc/neck_backward.hip): fp32 token-major rows, statistics of this process ----
+ * No atomics anywhere: every sum goes through per-workgroup partials in the workspace and one ordered pass, so two runs
+ * are bit-identical.  Every launch writes every element of its outputs; nothing syncs with the host.
+ *
+ * The forward of one conv + BatchNorm in training mode is the convolution without bias or activation (sdetr_neck_conv3x3,
+ * or a GEMM on the rows), then
+ *   sdetr_neck_bn_stats: per channel over `rows` rows of z (row stride ld): (count, mean, M2) per 64-row tile, merged in
+ *     tile order (Chan); stats f32 [2][channels] = (mean, 1 / sqrt(biased variance + eps)); running_mean / running_var (both
+ *     or both NULL) take the nn.BatchNorm2d update with `momentum` (the variance unbiased).  Workspace of
+ *     sdetr_neck_bn_stats_workspace_bytes.
+ *   sdetr_neck_bn_apply: out = act(gamma * (z - mean) * rstd + beta [+ alpha * (the same of z2 / stats2 / gamma2 / beta2)]),
+ *     act = SiLU when activation = 1: a RepVggPluXBlock's two norms in one launch.  z and z2 share the row stride ld_z.
+ *   sdetr_neck_gate_train: sdetr_neck_gate_shortcut's result for f32 rows y [batch, pixels, channels], which also stores
+ *     what the backward reads: logits f32 [batch, pixels] (mask_weight . y_p + mask_bias[0]) and saved f32
+ *     [batch][2 channels + 68] = gate [channels] | context [channels] | hidden after the ReLU [64] | softmax maximum, sum
+ *     of exponentials, 0, 0.  Workspace of sdetr_neck_gate_train_workspace_bytes.
+ *
+ * sdetr_neck_bwd_op, by kind (rows = batch * height * width; C = channels, K = out_channels, G = groups, k = kernel_size):
+ *   0 dgrad:  backward-data of a grouped convolution (k = 1 | 3, padding (k - 1) / 2, stride 1 | 2) whose input is
+ *             [batch, height, width, C]: dz [batch, Ho, Wo, K] dense, weight f32 [G][k][k][K / G][C / G] with the taps
+ *             FLIPPED (weight[g][a][b][o][i] = W[g K / G + o][i][k - 1 - a][k - 1 - b]), out [batch, height, width, C]
+ *             dense.  k = 3 with stride 1 runs sdetr_neck_conv3x3 on these weights.
+ *   1 wgrad:  backward-weight of the same convolution: dz as above, x the input rows (row stride ld_x), dweight f32
+ *             [K][C / G][k][k] (the parameter's layout).  Pixels are split over workgroups, partials go to the workspace
+ *             (at most 32 MiB), one ordered pass follows.  splits: 0 = automatic, n > 0 = n pixel chunks (clamped).
+ *   2 sum:    out = dz + add (+ x2), dense [rows, C].
+ *   3 norm:   BatchNorm backward with the SiLU derivative in front (act = 1): t = gamma * xh + beta (+ alpha * (gamma2 *
+ *             xh2 + beta2)), xh = (x - mean) * rstd recomputed from the stored pre-norm map x and stats (never from the
+ *             output: gamma may be zero), dt = dz * silu'(t); dbeta = sum dt, dgamma = sum dt * xh, out = gamma * rstd *
+ *             (dt - mean(dt) - xh * mean(dt * xh)); with x2: the second norm's dgamma2 / dbeta2 / out2, scaled by alpha.
+ *             dz has row stride ld_dz, x / x2 ld_x, out / out2 ld_out.  dgamma .. may be NULL (all of a norm or none).
+ *   4 gate:   backward of out = gate(ctx) * y + shortcut, ctx = sum_p softmax_p(m . y_p + b) y_p: dz = the gradient at
+ *             out, x = y, x2 = the forward's logits, stats = its saved block, gamma = m [C], weight = squeeze [hidden, C],
+ *             weight2 = excite [C, hidden]; out = the gradient at y (the shortcut's is dz itself), dgamma [C] / dbeta [1]
+ *             = d conv_mask.{weight, bias}, dweight / dweight2 = d se_module.{0, 2}.weight.  Per-image reductions in tile
+ *             order, the C / 16 MLP inside the kernel.  C <= 256, hidden <= 64.
+ *   5 upsample: backward of nearest up-sampling (the index rule of sdetr_neck_combine): dz [batch, height, width, C], out
+ *             [batch, src_height, src_width, C] = the sum of each coarse pixel's fine pixels, in row order.
+ * precision must be 0.  sdetr_neck_bwd_workspace_bytes: the largest need of a plan (-1: a bad op).  sdetr_neck_bwd_op_run
+ * runs one op; sdetr_neck_bwd_run a whole plan in order, validated before the first launch.  Channel counts and row
+ * strides are multiples of 4, tensors 16-byte aligned. */
+int64_t sdetr_neck_bn_stats_workspace_bytes(int64_t rows, int channels);
+int sdetr_neck_bn_stats(sdetr_stream_t stream, const float *z, int ld_z, int64_t rows, int channels, float eps,
+                        float momentum, float *running_mean, float *running_var, float *stats, void *workspace,
+                        int64_t workspace_bytes);
+int sdetr_neck_bn_apply(sdetr_stream_t stream, const float *z, const float *stats, const float *gamma, const float *beta,
+                        const float *z2, const float *stats2, const float *gamma2, const float *beta2, float alpha,
+                        int ld_z, int64_t rows, int channels, int activation, float *out, int ld_out);
+int64_t sdetr_neck_gate_train_workspace_bytes(int batch_size, int pixels, int channels);
+int sdetr_neck_gate_train(sdetr_stream_t stream, const float *y, int batch_size, int pixels, int channels,
+                          const float *mask_weight, const float *mask_bias, const float *squeeze_weight,
+                          const float *excite_weight, int hidden, const float *shortcut, int shortcut_row_stride,
+                          const float *shortcut2, int shortcut2_row_stride, float *logits, float *saved, void *workspace,
+                          int64_t workspace_bytes, float *out);
+
+typedef struct sdetr_neck_bwd_op {
+    int kind;
+    const float *dz;
+    const float *add;
+    const float *x;
+    const float *x2;
+    const float *weight;
+    const float *weight2;
+    const float *stats;
+    const float *gamma;
+    const float *beta;
+    const float *stats2;
+    const float *gamma2;
+    const float *beta2;
+    float *out;
+    float *out2;
+    float *dgamma;
+    float *dbeta;
+    float *dgamma2;
+    float *dbeta2;
+    float *dweight;
+    float *dweight2;
+    int batch;
+    int height;
+    int width;
+    int channels;
+    int out_channels;
+    int groups;
+    int kernel_size;
+    int stride;
+    int src_height;
+    int src_width;
+    int hidden;
+    int act;
+    int ld_dz;
+    int ld_x;
+    int ld_out;
+    int splits;
+    float alpha;
+    float eps;
+} sdetr_neck_bwd_op;
+
+int64_t sdetr_neck_bwd_workspace_bytes(const sdetr_neck_bwd_op *ops, int n_ops, int precision);
+int sdetr_neck_bwd_op_run(sdetr_stream_t stream, const sdetr_neck_bwd_op *op, int precision, void *workspace,
+                          int64_t workspace_bytes);
+int sdetr_neck_bwd_run(sdetr_stream_t stream, const sdetr_neck_bwd_op *ops, int n_ops, int precision, void *workspace,
+                       int64_t workspace_bytes);
+
 /* ---- fp32 GEMM on the bf16 matrix cores at fp32 accuracy (csrc/gemm_x3.hip) -- the Linear layers of the training
  * step (y = x w^T, dx = dy w, dw = dy^T x without transposed copies); replaces the at::linear / at::mm calls autograd
  * makes for nn.Linear (models/bricks/salience_transformer.py:347-351, ms_deform_attn.py:312-331).

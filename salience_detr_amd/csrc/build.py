@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["abi.hip", "msda_forward.hip", "msda_backward.hip", "msda_backward_tiled.hip", "msda_resident.hip", "topk.hip", "rows.hip", "plumbing.hip", "norm.hip", "salience_head.hip", "encoder_rows.hip", "ffn.hip", "token_linear.hip", "decoder_ops.hip", "proposals.hip", "salience_criterion.hip", "attention.hip", "topk_attention.hip", "gemm_x3.hip", "fused_head_value.hip", "neck.hip", "layer_norm_train.hip", "sampling_prep.hip", "attention_train.hip", "attention_train_masked.hip", "mlp_rows.hip", "post_process.hip", "set_criterion.hip", "frontend.hip", "frontend_backward.hip", "backbone.hip", "backbone_backward.hip", "convnext.hip", "convnext_backward.hip", "focalnet.hip", "swin.hip", "swin_backward.hip", "denoising.hip", "eval_resize.hip", "train_transform.hip", "optimizer.hip", "coco_eval.hip"]
+SOURCES = ["abi.hip", "msda_forward.hip", "msda_backward.hip", "msda_backward_tiled.hip", "msda_resident.hip", "topk.hip", "rows.hip", "plumbing.hip", "norm.hip", "salience_head.hip", "encoder_rows.hip", "ffn.hip", "token_linear.hip", "decoder_ops.hip", "proposals.hip", "salience_criterion.hip", "attention.hip", "topk_attention.hip", "gemm_x3.hip", "fused_head_value.hip", "neck.hip", "neck_backward.hip", "layer_norm_train.hip", "sampling_prep.hip", "attention_train.hip", "attention_train_masked.hip", "mlp_rows.hip", "post_process.hip", "set_criterion.hip", "frontend.hip", "frontend_backward.hip", "backbone.hip", "backbone_backward.hip", "convnext.hip", "convnext_backward.hip", "focalnet.hip", "swin.hip", "swin_backward.hip", "denoising.hip", "eval_resize.hip", "train_transform.hip", "optimizer.hip", "coco_eval.hip"]
 LIB = os.path.join(os.path.dirname(HERE), "libsalience_hip.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",

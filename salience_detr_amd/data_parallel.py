@@ -314,6 +314,12 @@ class StaticGradAllReducer:
             p.grad = v
 
 
+def _acc(t: torch.Tensor) -> torch.Tensor:
+    """``t`` in the type the norm computes in: float32, or float64 for a float64 tensor (a float64 reference run of the
+    composite keeps its precision; fp32 and 16-bit inputs compute exactly as before)."""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 class _SyncBatchNormTrain(torch.autograd.Function):
     """BatchNorm2d in training mode over ALL ranks' pixels (what ``nn.SyncBatchNorm`` gives the reference's neck under
     DDP, ``main.py:126-127``; single process: plain batch statistics).  One collective per direction instead of the
@@ -323,14 +329,15 @@ class _SyncBatchNormTrain(torch.autograd.Function):
     ``E[(x-s)^2] - E[x-s]^2`` then cancels only as far as the batch mean has moved from the running mean, not as far as
     it is from zero (torch's SyncBatchNorm merges per-rank mean / M2 instead, which needs the gathered per-rank
     statistics).  Running statistics are updated in place with the UNBIASED variance of the global batch
-    (``nn.BatchNorm2d`` semantics); ``weight`` / ``bias`` / running statistics may be ``None``."""
+    (``nn.BatchNorm2d`` semantics); ``weight`` / ``bias`` / running statistics may be ``None``.  Arithmetic in fp32,
+    in float64 for float64 inputs (``_acc``)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, group):
         C = x.shape[1]
-        xf = x.float()
+        xf = _acc(x)
         red = (0, 2, 3)
-        shift = running_mean.detach().float() if running_mean is not None else xf.new_zeros(C)
+        shift = _acc(running_mean.detach()) if running_mean is not None else xf.new_zeros(C)
         xs = xf - shift.view(1, C, 1, 1)
         stats = torch.cat([xs.sum(red), (xs * xs).sum(red), xf.new_tensor([xf.numel() / C])])
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -350,23 +357,23 @@ class _SyncBatchNormTrain(torch.autograd.Function):
         ctx.group, ctx.world, ctx.has_bias = group, world, bias is not None
         y = xhat
         if weight is not None:
-            y = y * weight.float().view(1, C, 1, 1)
+            y = y * _acc(weight).view(1, C, 1, 1)
         if bias is not None:
-            y = y + bias.float().view(1, C, 1, 1)
+            y = y + _acc(bias).view(1, C, 1, 1)
         return y.to(x.dtype)
 
     @staticmethod
     def backward(ctx, dy):
         xhat, weight, invstd, n = ctx.saved_tensors
         C = dy.shape[1]
-        dyf = dy.float()
+        dyf = _acc(dy)
         red = (0, 2, 3)
         sum_dy, sum_dy_xhat = dyf.sum(red), (dyf * xhat).sum(red)
         both = torch.cat([sum_dy, sum_dy_xhat])
         if ctx.world > 1:
             dist.all_reduce(both, op=dist.ReduceOp.SUM, group=ctx.group)
         g_mean, g_proj = both[:C] / n, both[C:] / n
-        scale = invstd if weight is None else weight.float() * invstd
+        scale = invstd if weight is None else _acc(weight) * invstd
         dx = (dyf - g_mean.view(1, C, 1, 1) - xhat * g_proj.view(1, C, 1, 1)) * scale.view(1, C, 1, 1)
         # parameter gradients stay LOCAL sums: the gradient all-reduce of the step adds the ranks' contributions
         gw = sum_dy_xhat.to(weight.dtype) if weight is not None else None
