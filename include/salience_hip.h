@@ -1437,6 +1437,21 @@ int sdetr_frontend_masks_positions(sdetr_stream_t stream, const uint8_t *mask, i
  * fixed order through the workspace (no atomics: bit-identical from run to run).  x and weight 16-byte aligned.
  * A max-pool op (op 1): 3x3 stride 2 padding 1 over x channels-last [batch, height, width, in_channels] (in % 8 == 0)
  * into out [batch, Ho, Wo, in_channels], compute dtype, padding never selected.
+ * A deformable conv op (op 2): the modulated deformable 3x3 product of a DCN stage (models/bricks/deform_conv2d_pack.py
+ * on torchvision's deform_conv2d contract), groups 1, offset groups 1, dilation 1: x, weight (layout 0), bias, residual,
+ * out, out_nchw and relu as op 0; kernel_size 3, padding 1, stride 1 or 2, in % 32 == 0, out_channels % 8 == 0, x_nchw 0.
+ * offset_mask f32 [batch, Ho, Wo, 32] (16-byte aligned): channel 2 t = dy and 2 t + 1 = dx of tap t = ky * 3 + kx,
+ * 18 + t = the mask LOGIT of tap t (the op applies the sigmoid), 27..31 unread.  Tap t of output pixel (oy, ox) samples x
+ * at (oy * stride - 1 + ky + dy, ox * stride - 1 + kx + dx), bilinear; the sample is zero at y <= -1, y >= height,
+ * x <= -1 or x >= width, otherwise every corner outside the map contributes zero; the sample times sigmoid(logit) enters
+ * the product in op 0's reduction order.  Precision 0 splits the sampled fp32 value three ways as op 0 splits x; precision 1
+ * sums the four corners in fp32 and rounds once to the 16-bit type.  No offset value, finite or not, reads outside x: the
+ * coordinate is clamped to [-1, height] x [-1, width] in float before the floor, corner addresses are clamped into the
+ * map.  The reduction is never split: `splits` is ignored, sdetr_backbone_conv_splits answers 1, the workspace is 0 bytes.
+ * An exact conv op (op 3): op 0 whose product is the exact three-way split at EITHER precision (weight packed with
+ * precision 0) and whose out is f32 [batch, Ho, Wo, out_channels]; x is the compute dtype's channels-last tensor (at
+ * precision 1 the 16-bit activation, which splits exactly), no residual.  It computes the offset_mask of an op 2: the
+ * offset and mask convs as one conv of 27 channels zero-padded to 32, their biases packed as beta with a unit norm.
  * sdetr_backbone_run launches a whole plan of ops in order (validated before the first launch); the workspace must hold
  * sdetr_backbone_workspace_bytes (the largest split-K buffer of the plan).
  *
@@ -1495,6 +1510,7 @@ typedef struct sdetr_backbone_op {
     int relu;
     int x_nchw;
     int splits;
+    const float *offset_mask;
 } sdetr_backbone_op;
 
 int64_t sdetr_backbone_packed_bytes(int out_channels, int in_channels, int kernel_size, int precision);

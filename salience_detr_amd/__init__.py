@@ -6,7 +6,8 @@ _LAZY = {"GenerateCDNQueries": "denoising", "SalienceDETR": "detector", "Salienc
          "ConvNeXtBackbone": "convnext", "CNBlockConfig": "convnext", "FocalNetBackbone": "focalnet",
          "SwinBackbone": "swin", "TrainTransform": "train_transform", "TrainBatch": "train_transform",
          "AugmentParams": "train_transform", "sample_params": "train_transform", "shortest_size": "train_transform",
-         "transform_targets": "train_transform", "CocoBoxEvaluator": "coco_eval", "evaluate": "coco_eval"}
+         "transform_targets": "train_transform", "CocoBoxEvaluator": "coco_eval", "evaluate": "coco_eval",
+         "deform_conv2d": "deform_conv", "DeformConv2d": "deform_conv", "DeformConv2dPack": "deform_conv"}
 
 
 def __getattr__(name):

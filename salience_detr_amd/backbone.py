@@ -18,8 +18,11 @@ How it runs (inference: grad disabled, or nothing that requires grad) -- ``csrc/
     backbones' are) handed to ``sdetr_backbone_run`` (one ctypes call per forward);
   * ``set_dtype``: fp32 (default) multiplies at fp32 accuracy (exact three-way bf16 split of both operands); bf16 /
     fp16 take one 16-bit product with fp32 accumulation and keep the activations in that type between layers.
-The HIP path serves every ``groups == 1`` arch without dilation or DCN: resnet18/34/50/101/152 and wide_resnet50_2 /
-101_2.  Grouped ResNeXt, and by default every call with grad enabled on something that requires grad, take the
+The HIP path serves every ``groups == 1`` arch without dilation: resnet18/34/50/101/152 and wide_resnet50_2 / 101_2,
+with or without deformable stages.  A DCN stage (``stage_with_dcn``, ``deform_conv.DeformConv2dPack`` as ``conv2``) is
+two ops per block: the offset and mask convs as ONE exact conv (27 channels padded to 32, fp32 out, the three-way split
+whatever ``set_dtype`` says: an offset is a coordinate), then the deformable product, whose A tile is the masked bilinear
+gather and whose weight, epilogue and tiles are the plain conv's.  Grouped ResNeXt (with or without DCN), and by default every call with grad enabled on something that requires grad, take the
 plain-torch composite (``F.conv2d`` + the frozen affine), which is also the default autograd path.  A CPU tensor on the
 HIP form raises: the hot path has no CPU fallback.
 
@@ -31,7 +34,9 @@ one backward-data launch per conv whose input has a trainable conv upstream, one
 conv (plus the fixed-order reduction where a reduction is split), one ingest launch per returned map.  The stored
 activations are the ReLU masks and the weight-gradient operands; no activation is copied.  Served: ``hip_form()``
 archs with a frozen stem (``freeze_indices`` non-empty), an input without gradient, float32 or bfloat16; anything else
-raises at forward.  Stem / max-pool backward and float16 training are out of scope.
+raises at forward.  Stem / max-pool backward, float16 training and the deformable backward are out of scope: a DCN conv
+that is trainable, or that a gradient has to pass through (something trainable upstream of it), raises with that reason;
+frozen DCN stages below the lowest trainable conv do not stand in the way.
 """
 import ctypes
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Type, Union
@@ -41,6 +46,7 @@ from torch import Tensor, nn
 
 from . import _hip
 from .backbone_base import HipBackbone
+from .deform_conv import DeformConv2dPack
 from .derived import derived
 from .hip_module import PlanBuilder
 
@@ -78,6 +84,16 @@ def conv3x3(in_planes: int, out_planes: int, stride: int = 1, groups: int = 1, d
                      dilation=dilation)
 
 
+def conv3x3_dcn(in_planes: int, out_planes: int, stride: int = 1, groups: int = 1, dilation: int = 1) -> DeformConv2dPack:
+    return DeformConv2dPack(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, groups=groups, bias=False,
+                            dilation=dilation)
+
+
+def _core(conv: nn.Module) -> nn.Module:
+    """The module that holds a conv's geometry and main weight: a ``DeformConv2dPack``'s ``deform_conv2d``, else itself."""
+    return conv.deform_conv2d if isinstance(conv, DeformConv2dPack) else conv
+
+
 def conv1x1(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
     return nn.Conv2d(in_planes, out_planes, kernel_size=1, stride=stride, bias=False)
 
@@ -94,12 +110,10 @@ class BasicBlock(nn.Module):
             raise ValueError("BasicBlock only supports groups=1 and base_width=64")
         if dilation > 1:
             raise NotImplementedError("Dilation > 1 not supported in BasicBlock")
-        if with_dcn:
-            raise NotImplementedError("deformable conv stages are not available (no DeformConv2d in this package)")
         self.conv1 = conv3x3(inplanes, planes, stride)
         self.bn1 = norm_layer(planes)
         self.relu = nn.ReLU(inplace=True)
-        self.conv2 = conv3x3(planes, planes)
+        self.conv2 = conv3x3_dcn(planes, planes) if with_dcn else conv3x3(planes, planes)
         self.bn2 = norm_layer(planes)
         self.downsample = downsample
         self.stride = stride
@@ -120,12 +134,10 @@ class Bottleneck(nn.Module):
                  with_dcn: bool = False):
         super().__init__()
         norm_layer = norm_layer or FrozenBatchNorm2d
-        if with_dcn:
-            raise NotImplementedError("deformable conv stages are not available (no DeformConv2d in this package)")
         width = int(planes * (base_width / 64.0)) * groups
         self.conv1 = conv1x1(inplanes, width)
         self.bn1 = norm_layer(width)
-        self.conv2 = conv3x3(width, width, stride, groups, dilation)
+        self.conv2 = (conv3x3_dcn if with_dcn else conv3x3)(width, width, stride, groups, dilation)
         self.bn2 = norm_layer(width)
         self.conv3 = conv1x1(width, planes * self.expansion)
         self.bn3 = norm_layer(planes * self.expansion)
@@ -265,11 +277,16 @@ class ResNetBackbone(HipBackbone):
 
     # ------------------------------------------------------------------------------------------ form checks
     def _convs(self):
+        """Every conv of the network; a ``DeformConv2dPack`` is ONE conv (its ``deform_conv2d``; the offset and mask convs
+        inside it are part of that conv's HIP form)."""
         yield self.conv1
         for stage in self.stages():
             for blk in stage:
+                inner = {id(c) for m in blk.modules() if isinstance(m, DeformConv2dPack) for c in (m.conv_offset, m.conv_mask)}
                 for m in blk.modules():
-                    if isinstance(m, nn.Conv2d):
+                    if isinstance(m, DeformConv2dPack):
+                        yield m.deform_conv2d
+                    elif isinstance(m, nn.Conv2d) and id(m) not in inner:
                         yield m
 
     def hip_form(self) -> bool:
@@ -277,8 +294,10 @@ class ResNetBackbone(HipBackbone):
         if self.groups != 1 or self.dilation != 1:
             return False
         for c in self._convs():
-            if c.groups != 1 or c.dilation != (1, 1) or c.bias is not None:
+            if c.groups != 1 or tuple(c.dilation) != (1, 1) or c.bias is not None:
                 return False
+            if not isinstance(c, nn.Conv2d) and (tuple(c.kernel_size) != (3, 3) or tuple(c.padding) != (1, 1)):
+                return False   # (the deformable product is the 3x3 one)
             if c is not self.conv1 and (c.in_channels % 32 or c.out_channels % 8):
                 return False
         norms = [self.bn1] + [m for stage in self.stages() for blk in stage for name, m in blk.named_modules()
@@ -307,18 +326,57 @@ class ResNetBackbone(HipBackbone):
         return derived(conv, "backbone_packed", sources, build,
                        extra=(float(bn.eps), self._precision(), self.compute_dtype, layout))
 
+    def _packed_offset_mask(self, pack: DeformConv2dPack) -> Tuple[Tensor, Tensor]:
+        """``(packed weight, bias [32])`` of ``conv_offset`` and ``conv_mask`` as one 3x3 conv: 18 + 9 channels, zero rows up
+        to 32, the two biases as the folded bias (a unit norm); ALWAYS the three exact planes (precision 0).  Built once
+        per parameter version."""
+        off, msk = pack.conv_offset, pack.conv_mask
+        sources = (off.weight, off.bias, msk.weight, msk.bias)
+
+        def build():
+            dev, n_off, n_msk = off.weight.device, off.out_channels, msk.out_channels
+            w32 = torch.zeros((32, off.in_channels, 3, 3), dtype=torch.float32, device=dev)
+            beta = torch.zeros(32, dtype=torch.float32, device=dev)
+            w32[:n_off], w32[n_off:n_off + n_msk] = off.weight.detach().float(), msk.weight.detach().float()
+            beta[:n_off], beta[n_off:n_off + n_msk] = off.bias.detach().float(), msk.bias.detach().float()
+            unit = (torch.ones(32, device=dev), beta, torch.zeros(32, device=dev), torch.ones(32, device=dev))
+            return self._pack(w32, unit, 0.0, 0, precision=0)
+        return derived(pack, "backbone_packed_offset_mask", sources, build)
+
     def build_plan(self, x: Tensor, splits: int = 0, acts: Optional[Dict[str, Tensor]] = None):
         """The op list of one forward on ``x`` ``[B, 3, H, W]`` (fp32 NCHW on the device): ``(ops, outputs, keep, names)``:
         ``outputs`` the returned fp32 NCHW maps, ``keep`` every tensor the plan points into, ``names`` one label per op
         (``"conv1"``, ``"pool"``, ``"layer2.0.conv1"``, ``"layer2.0.downsample.0"`` ..).  ``acts`` (a dict) receives the
         channels-last output of every op under the op's name, in op order: what the training backward reads."""
-        names = {id(m): n for n, m in self.named_modules() if isinstance(m, nn.Conv2d)}
+        names = {id(m): n for n, m in self.named_modules() if isinstance(m, (nn.Conv2d, DeformConv2dPack))}
         act = torch.float32 if self._precision() == 0 else self.compute_dtype
         batch = x.shape[0]
         pb = PlanBuilder(_hip.BackboneOpStruct, x, batch=batch)
         new, keep, outputs = pb.new, pb.keep, pb.outputs
 
+        def dcn_op(pack, bn, src, h, w, relu, residual=None, nchw_out=None):
+            """A DCN conv: its offsets and mask logits (an exact conv, fp32 rows of 32), then the deformable product."""
+            dc, name = pack.deform_conv2d, names[id(pack)]
+            s = dc.stride[0]
+            ho, wo = _out_hw(h, 3, s, 1), _out_hw(w, 3, s, 1)
+            om_packed, om_bias = self._packed_offset_mask(pack)
+            packed, bias = self._packed_conv_bn(dc, bn, 0)
+            keep.extend((om_packed, om_bias, packed, bias))
+            om = new((batch, ho, wo, 32), torch.float32)
+            out = new((batch, ho, wo, dc.out_channels), act)
+            if acts is not None:
+                acts[name + ".offset"], acts[name] = om, out
+            shape = dict(in_channels=dc.in_channels, height=h, width=w, kernel_size=3, stride=s, padding=1, x_nchw=0)
+            pb.op(name + ".offset", 3, x=src.data_ptr(), weight=om_packed.data_ptr(), bias=om_bias.data_ptr(), out=om.data_ptr(),
+                  out_channels=32, relu=0, splits=splits, **shape)
+            pb.op(name, 2, x=src.data_ptr(), weight=packed.data_ptr(), bias=bias.data_ptr(), residual=_hip.ptr(residual),
+                  out=out.data_ptr(), out_nchw=_hip.ptr(nchw_out), out_channels=dc.out_channels, relu=1 if relu else 0,
+                  splits=0, offset_mask=om.data_ptr(), **shape)
+            return out, ho, wo
+
         def conv_op(conv, bn, src, h, w, relu, residual=None, nchw_out=None, x_nchw=False):
+            if isinstance(conv, DeformConv2dPack):
+                return dcn_op(conv, bn, src, h, w, relu, residual, nchw_out)
             k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
             ho, wo = _out_hw(h, k, s, p), _out_hw(w, k, s, p)
             packed, bias = self._packed_conv_bn(conv, bn, 1 if x_nchw else 0)
@@ -362,7 +420,7 @@ class ResNetBackbone(HipBackbone):
 
     @staticmethod
     def _block_out_channels(blk) -> int:
-        return blk.conv3.out_channels if isinstance(blk, Bottleneck) else blk.conv2.out_channels
+        return blk.conv3.out_channels if isinstance(blk, Bottleneck) else _core(blk.conv2).out_channels
 
     def forward_hip(self, x: Tensor, splits: int = 0, state: Optional[dict] = None) -> Dict[str, Tensor]:
         """``state`` (a dict): a training forward; it receives ``"acts"``, see ``build_plan``."""
@@ -380,6 +438,20 @@ class ResNetBackbone(HipBackbone):
     train_reasons = ("the architecture is not one the HIP kernels serve (grouped / dilated convs, a bias or a norm layer "
                      "other than FrozenBatchNorm2d)",
                      "the stem (conv1) is not frozen: the stem and max-pool backward are out of scope")
+    dcn_train_reason = ("a deformable conv (DCN) stage is trainable or has something trainable upstream of it: the "
+                        "deformable backward in HIP is out of scope (freeze the DCN stages and everything below them, or "
+                        "train through the composite)")
+
+    def _extra_train_reason(self) -> Optional[str]:
+        """The DCN rule: no weight gradient of, and no data gradient through, a deformable conv."""
+        upstream = False   # a trainable parameter below the current block
+        for stage in self.stages():
+            for blk in stage:
+                if isinstance(blk.conv2, DeformConv2dPack) and (
+                        upstream or blk.conv1.weight.requires_grad or any(p.requires_grad for p in blk.conv2.parameters())):
+                    return self.dcn_train_reason
+                upstream = upstream or any(p.requires_grad for p in blk.parameters())
+        return None
 
     def _stem_modules(self):
         return self.conv1, self.bn1
@@ -398,7 +470,7 @@ class ResNetBackbone(HipBackbone):
                 prefix = f"layer{i + 1}.{j}"
                 chain, ch, cw = [], h, w
                 for n in ("conv1", "conv2", "conv3") if isinstance(blk, Bottleneck) else ("conv1", "conv2"):
-                    conv = getattr(blk, n)
+                    conv = _core(getattr(blk, n))
                     chain.append((f"{prefix}.{n}", conv, getattr(blk, "bn" + n[-1]), ch, cw))
                     ch, cw = (_out_hw(v, conv.kernel_size[0], conv.stride[0], conv.padding[0]) for v in (ch, cw))
                 ds = None if blk.downsample is None else (f"{prefix}.downsample.0", blk.downsample[0], blk.downsample[1], h, w)
@@ -488,7 +560,8 @@ class ResNetBackbone(HipBackbone):
         """Test hook (read-only): ``(op name, post-activation output [B, H, W, C] in the compute dtype)`` of every op with
         a ReLU, in op order (the stem first), as stored by the last ``"hip"`` training forward.  Valid while that
         forward's autograd graph is alive."""
-        return [(n, t) for n, t in self._train_state()["acts"].items() if n != "pool" and ".downsample." not in n]
+        return [(n, t) for n, t in self._train_state()["acts"].items()
+                if n != "pool" and ".downsample." not in n and not n.endswith(".offset")]
 
     backward_struct, backward_prefix = _hip.BackboneBwdOpStruct, "sdetr_backbone_bwd"
 

@@ -8,6 +8,10 @@
 //                             epilogue relu?(acc + b'[co] (+ residual)), channels-last output in the compute dtype and,
 //                             for the last block of a returned stage, an fp32 NCHW copy; split over K when the tile grid
 //                             is small, the pieces summed in a fixed order by backbone_splitk_kernel (no atomics)
+//                             The same kernel with another A-tile loader (backbone_conv_core.h) is the modulated
+//                             deformable 3x3 product of a DCN stage (op 2: four masked bilinear corners per tap summed
+//                             into the tile, fp32 or rounded once to 16 bits) and the exact product on 16-bit
+//                             activations in front of it (op 3: the offsets and mask logits, fp32 out at any precision)
 //   backbone_maxpool_kernel   3x3 stride-2 pad-1 max pool, channels-last
 //   backbone_batch_kernel     normalise (ImageNet mean / std) and pad a list of images into one canvas + padding mask
 //
@@ -142,10 +146,13 @@ __global__ void __launch_bounds__(256) backbone_batch_kernel(BatchArgs a)
 
 // ------------------------------------------------------------------------------------------------------------ host
 
-// validated kernel arguments of one conv op (precision 0 fp32, 1 the library's 16-bit type)
+// validated kernel arguments of one conv op (precision 0 fp32, 1 the library's 16-bit type).  Kinds: 0 the conv; 2 the
+// deformable product (kernel 3, padding 1, the reduction never split); 3 the exact conv (three-plane weight and fp32 output
+// at either precision, no residual).
 int make_conv(const sdetr_backbone_op &o, int precision, BConv &c)
 {
-    const char *what = "sdetr_backbone (conv)";
+    const char *what = o.op == 2 ? "sdetr_backbone (deformable conv)" : o.op == 3 ? "sdetr_backbone (exact conv)"
+                                                                                  : "sdetr_backbone (conv)";
     if (precision != 0 && precision != 1) return fail("%s: precision must be 0 or 1", what);
     if (!o.x || !o.weight || !o.bias || !o.out) return fail("%s: null tensor", what);
     if (o.batch < 1 || o.in_channels < 1 || o.out_channels < 1 || o.height < 1 || o.width < 1)
@@ -156,15 +163,26 @@ int make_conv(const sdetr_backbone_op &o, int precision, BConv &c)
         return fail("%s: unsupported kernel %d / stride %d / padding %d", what, o.kernel_size, o.stride, o.padding);
     if (o.x_nchw == 0 && o.in_channels % 32)
         return fail("%s: a channels-last input needs in_channels %% 32 == 0 (got %d)", what, o.in_channels);
+    if (o.op != 0 && o.x_nchw) return fail("%s: the input is channels-last (x_nchw must be 0)", what);
+    if (o.op == 2) {
+        if (o.kernel_size != 3 || o.padding != 1)
+            return fail("%s: kernel 3 with padding 1 only (got kernel %d, padding %d)", what, o.kernel_size, o.padding);
+        if (o.out_channels % 8) return fail("%s: out_channels %% 8 == 0 (got %d)", what, o.out_channels);
+        if (!o.offset_mask) return fail("%s: null offset / mask tensor", what);
+        if (reinterpret_cast<uintptr_t>(o.offset_mask) & 15) return fail("%s: offset_mask must be 16-byte aligned", what);
+    }
+    if (o.op == 3 && o.residual) return fail("%s: takes no residual", what);
     if ((reinterpret_cast<uintptr_t>(o.x) | reinterpret_cast<uintptr_t>(o.weight)) & 15)
         return fail("%s: x and weight must be 16-byte aligned", what);
     const int ho = out_hw(o.height, o.kernel_size, o.stride, o.padding), wo = out_hw(o.width, o.kernel_size, o.stride, o.padding);
     if (ho < 1 || wo < 1) return fail("%s: empty output", what);
     const ConvGeom g = {o.x, o.weight, o.bias, o.residual, o.out, o.batch, o.in_channels, o.height, o.width, o.out_channels,
-                        o.kernel_size, o.stride, o.padding, ho, wo, o.x_nchw, o.splits};
-    if (int rc = fill_conv(what, g, precision, c)) return rc;
+                        o.kernel_size, o.stride, o.padding, ho, wo, o.x_nchw, o.op == 2 ? 1 : o.splits};
+    if (int rc = fill_conv(what, g, o.op == 3 ? 0 : precision, c)) return rc;
+    if (o.op == 3 && precision == 1) c.x_bytes /= 2;   // the 16-bit activation under the three-plane weight
     c.out_nchw = o.out_nchw;
     c.relu = o.relu ? 1 : 0;
+    c.om = o.op == 2 ? o.offset_mask : nullptr;
     return 0;
 }
 
@@ -177,10 +195,20 @@ int run_conv(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws,
                     (long long)conv_workspace(c));
     c.partial = reinterpret_cast<float *>(ws);
     const bool x3 = precision == 0;
-    if (x3 && o.x_nchw) launch_conv<true, true, 0>(s, c);
-    else if (x3) launch_conv<true, false, 0>(s, c);
-    else if (o.x_nchw) launch_conv<false, true, 0>(s, c);
-    else launch_conv<false, false, 0>(s, c);
+    if (o.op == 2) {
+        if (x3) launch_conv<true, kADeform, 0>(s, c);
+        else launch_conv<false, kADeform, 0>(s, c);
+        return check_launch("sdetr_backbone (deformable conv)");
+    }
+    if (o.op == 3) {
+        if (x3) launch_conv<true, kANhwc, 0>(s, c);
+        else launch_conv<true, kAWiden, 0>(s, c);
+        return check_launch("sdetr_backbone (exact conv)");
+    }
+    if (x3 && o.x_nchw) launch_conv<true, kANchw, 0>(s, c);
+    else if (x3) launch_conv<true, kANhwc, 0>(s, c);
+    else if (o.x_nchw) launch_conv<false, kANchw, 0>(s, c);
+    else launch_conv<false, kANhwc, 0>(s, c);
     return check_launch("sdetr_backbone (conv)");
 }
 
@@ -218,7 +246,7 @@ int run_maxpool(hipStream_t s, const sdetr_backbone_op &o, int precision)
 int check_op(const sdetr_backbone_op &o, int precision, int64_t &need)
 {
     need = 0;
-    if (o.op == 0) {
+    if (o.op == 0 || o.op == 2 || o.op == 3) {
         BConv c;
         if (int rc = make_conv(o, precision, c)) return rc;
         need = conv_workspace(c);
@@ -230,7 +258,7 @@ int check_op(const sdetr_backbone_op &o, int precision, int64_t &need)
 
 int run_op(hipStream_t s, const sdetr_backbone_op &o, int precision, void *ws, int64_t ws_bytes)
 {
-    if (o.op == 0) return run_conv(s, o, precision, ws, ws_bytes);
+    if (o.op == 0 || o.op == 2 || o.op == 3) return run_conv(s, o, precision, ws, ws_bytes);
     if (o.op == 1) return run_maxpool(s, o, precision);
     return fail("sdetr_backbone: unknown op kind %d", o.op);
 }
@@ -269,7 +297,7 @@ extern "C" int sdetr_backbone_pack(sdetr_stream_t stream, const float *weight, c
 extern "C" int sdetr_backbone_conv_splits(const sdetr_backbone_op *op, int precision)
 {
     BConv c;
-    if (!op || op->op != 0) return fail("sdetr_backbone_conv_splits: not a conv op");
+    if (!op || (op->op != 0 && op->op != 2 && op->op != 3)) return fail("sdetr_backbone_conv_splits: not a conv op");
     if (make_conv(*op, precision, c)) return SDETR_EINVAL;
     return c.splits;
 }
@@ -282,7 +310,7 @@ extern "C" int64_t sdetr_backbone_workspace_bytes(const sdetr_backbone_op *ops, 
 extern "C" int sdetr_backbone_conv(sdetr_stream_t stream, const sdetr_backbone_op *op, int precision, void *workspace,
                                    int64_t workspace_bytes)
 {
-    if (!op || op->op != 0) return fail("sdetr_backbone_conv: not a conv op");
+    if (!op || (op->op != 0 && op->op != 2 && op->op != 3)) return fail("sdetr_backbone_conv: not a conv op");
     return run_op((hipStream_t)stream, *op, precision, workspace, workspace_bytes);
 }
 

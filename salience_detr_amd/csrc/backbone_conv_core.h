@@ -31,7 +31,12 @@ struct BConv {
     const float *q;         // EPI 3 / 4: the fp32 multiplier rows, element (m, co) at q[m * ldq + co]; EPI 7: q[n]
     int ldq;
     char *aux;              // EPI 6: the pre-GELU values [M][co], compute dtype
+    const float *om;        // kADeform: the offset / mask rows [M][32] fp32 (18 offsets, 9 mask logits, 5 unused)
 };
+
+// how the A tile is staged: channels-last rows, the stem's NCHW gather, the deformable gather (four masked bilinear
+// corners per tap), 16-bit channels-last rows widened to fp32 (the three-way split on 16-bit activations)
+constexpr int kANhwc = 0, kANchw = 1, kADeform = 2, kAWiden = 3;
 
 // where output pixel m reads its taps: input row / column of tap (0, 0) and the image's first element
 struct RowInfo {
@@ -84,6 +89,133 @@ struct ALoadNHWC {
         char *d = tile + (tid >> kShift) * row + 16 * (tid & ((1 << kShift) - 1));
 #pragma unroll
         for (int j = 0; j < kRows; ++j) *reinterpret_cast<uint4 *>(d + kStep * j * row) = v[j];
+    }
+};
+
+// A tile of the exact product on 16-bit activations (the offset / mask conv of a deformable conv in 16-bit mode): the
+// 16-bit rows of ALoadNHWC<false>, stored as the fp32 rows the three-way split reads (a 16-bit value splits exactly)
+struct ALoadWiden : ALoadNHWC<false> {
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        char *d = tile + (tid >> 2) * kBRow32 + 32 * (tid & 3);
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            const uint4 q = v[j];
+            float4 *o = reinterpret_cast<float4 *>(d + kStep * j * kBRow32);
+            o[0] = make_float4(act_lo(q.x), act_hi(q.x), act_lo(q.y), act_hi(q.y));
+            o[1] = make_float4(act_lo(q.z), act_hi(q.z), act_lo(q.w), act_hi(q.w));
+        }
+    }
+};
+
+// A tile of the modulated deformable 3x3 product: the thread layout of ALoadNHWC, but a tap's 32 channels of a pixel row
+// are sum_corner w[corner] * x[corner, c0 .. c0 + 31] with w = bilinear weight * sigmoid(mask logit), zero for a corner
+// outside the map and for a sample at y <= -1, y >= H, x <= -1 or x >= W.  The corner rows and weights are computed once
+// per tap (a tap spans ci / 32 reduction steps) from the fp32 offset / mask rows c.om.
+//
+// Addressing: the sample row is by + dy with by the tap's integer row; the coordinate is clamped to [-1, H] in float
+// BEFORE the floor and the integer conversion, written on the offset (dy clamped to [-1 - by, H - by], both exact small
+// integers) so that floor(by + dy) = by + floor(dy) and the fraction is dy's own: no rounding of the sum, and no offset
+// value (huge, infinite, NaN: fmaxf / fminf drop a NaN) reaches the conversion.  Every corner address is clamped into the
+// map, an out-of-range corner has weight zero; a row past M reads pixel 0 with weight zero.
+template <bool X3>
+struct ALoadDeform {
+    static constexpr int kRows = X3 ? 4 : 2, kStep = X3 ? 64 : 128, kShift = X3 ? 3 : 2, kEsz = X3 ? 4 : 2;
+    int row0, tap_at;
+    uint32_t off[kRows][4];   // byte offset of the corner pixel's channel 0: (y0, x0), (y0, x1), (y1, x0), (y1, x1)
+    float wt[kRows][4];
+    uint4 v[kRows][4];
+    __device__ __forceinline__ void init(const BConv &c, int m0, int tid)
+    {
+        row0 = m0 + (tid >> kShift);
+        tap_at = -1;
+    }
+    __device__ __forceinline__ void corners(const BConv &c, int tap)
+    {
+        const int ky = tap / 3, kx = tap - 3 * ky;
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            const int m = row0 + kStep * j;
+            if (m >= c.M) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) off[j][q] = 0u, wt[j][q] = 0.f;
+                continue;
+            }
+            const float *om = c.om + (int64_t)m * 32;
+            const RowInfo ri = row_info(c, m, c.h * c.w_in);   // (once per tap: cheaper than nine live registers per row)
+            const int by = ri.iy0 + ky, bx = ri.ix0 + kx;
+            const float ylo = (float)(-1 - by), yhi = (float)(c.h - by), xlo = (float)(-1 - bx), xhi = (float)(c.w_in - bx);
+            const float dy = fminf(fmaxf(om[2 * tap], ylo), yhi), dx = fminf(fmaxf(om[2 * tap + 1], xlo), xhi);
+            const bool inside = dy > ylo && dy < yhi && dx > xlo && dx < xhi;
+            const float fy = floorf(dy), fx = floorf(dx), ly = dy - fy, lx = dx - fx, hy = 1.f - ly, hx = 1.f - lx;
+            const int y0 = by + (int)fy, x0 = bx + (int)fx, y1 = y0 + 1, x1 = x0 + 1;   // in [-1, H] x [-1, W]
+            const float mod = inside ? 1.f / (1.f + expf(-om[18 + tap])) : 0.f;
+            const bool y0v = y0 >= 0 && y0 < c.h, y1v = y1 >= 0 && y1 < c.h, x0v = x0 >= 0 && x0 < c.w_in, x1v = x1 >= 0 && x1 < c.w_in;
+            const uint32_t y0c = (uint32_t)min(max(y0, 0), c.h - 1), y1c = (uint32_t)min(max(y1, 0), c.h - 1);
+            const uint32_t x0c = (uint32_t)min(max(x0, 0), c.w_in - 1), x1c = (uint32_t)min(max(x1, 0), c.w_in - 1);
+            const uint32_t r0 = (uint32_t)ri.base + y0c * (uint32_t)c.w_in, r1 = (uint32_t)ri.base + y1c * (uint32_t)c.w_in;
+            const uint32_t pixel = (uint32_t)c.ci * kEsz;
+            off[j][0] = (r0 + x0c) * pixel;
+            off[j][1] = (r0 + x1c) * pixel;
+            off[j][2] = (r1 + x0c) * pixel;
+            off[j][3] = (r1 + x1c) * pixel;
+            wt[j][0] = y0v && x0v ? hy * hx * mod : 0.f;
+            wt[j][1] = y0v && x1v ? hy * lx * mod : 0.f;
+            wt[j][2] = y1v && x0v ? ly * hx * mod : 0.f;
+            wt[j][3] = y1v && x1v ? ly * lx * mod : 0.f;
+        }
+    }
+    __device__ __forceinline__ void load(const BConv &c, __amdgpu_buffer_rsrc_t rs, int k0, int kend, int tid)
+    {
+        if (k0 >= kend) {   // (uniform; K is whole reduction tiles here, so the pipeline never asks)
+#pragma unroll
+            for (int j = 0; j < kRows; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[j][q] = make_uint4(0u, 0u, 0u, 0u);
+            return;
+        }
+        const int tap = k0 / c.ci, c0 = k0 - tap * c.ci;
+        if (tap != tap_at) {   // (uniform)
+            corners(c, tap);
+            tap_at = tap;
+        }
+        const uint32_t piece = (uint32_t)c0 * kEsz + 16u * (uint32_t)(tid & ((1 << kShift) - 1));
+#pragma unroll
+        for (int j = 0; j < kRows; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[j][q] = buffer_load16(rs, off[j][q] + piece);
+    }
+    __device__ __forceinline__ void store(char *tile, int tid) const
+    {
+        constexpr int row = X3 ? kBRow32 : kBRow16;
+        char *d = tile + (tid >> kShift) * row + 16 * (tid & ((1 << kShift) - 1));
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            uint4 r;
+            if (X3) {
+                float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t u[4] = {v[j][q].x, v[j][q].y, v[j][q].z, v[j][q].w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) s[i] = fmaf(wt[j][q], __uint_as_float(u[i]), s[i]);
+                }
+                r = make_uint4(__float_as_uint(s[0]), __float_as_uint(s[1]), __float_as_uint(s[2]), __float_as_uint(s[3]));
+            } else {   // the four corners summed in fp32, rounded once
+                float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t u[4] = {v[j][q].x, v[j][q].y, v[j][q].z, v[j][q].w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        s[2 * i] = fmaf(wt[j][q], act_lo(u[i]), s[2 * i]);
+                        s[2 * i + 1] = fmaf(wt[j][q], act_hi(u[i]), s[2 * i + 1]);
+                    }
+                }
+                r = make_uint4(pack_act2(s[0], s[1]), pack_act2(s[2], s[3]), pack_act2(s[4], s[5]), pack_act2(s[6], s[7]));
+            }
+            *reinterpret_cast<uint4 *>(d + kStep * j * row) = r;
+        }
     }
 };
 
@@ -199,7 +331,7 @@ __device__ __forceinline__ void emit(const BConv &c, int m, int co, float v)
     }
 }
 
-template <bool X3, bool NCHW, int EPI>
+template <bool X3, int AM, int EPI>
 __global__ void __launch_bounds__(kBThreads, 1) backbone_conv_kernel(BConv c)
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -220,7 +352,10 @@ __global__ void __launch_bounds__(kBThreads, 1) backbone_conv_kernel(BConv c)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[rt][ct][i] = 0.f;
 
-    typename std::conditional<NCHW, ALoadNCHW<X3>, ALoadNHWC<X3>>::type ta;
+    static_assert(AM != kAWiden || X3, "widened 16-bit rows feed the three-way split only");
+    typename std::conditional<AM == kANchw, ALoadNCHW<X3>,
+        typename std::conditional<AM == kADeform, ALoadDeform<X3>,
+            typename std::conditional<AM == kAWiden, ALoadWiden, ALoadNHWC<X3>>::type>::type>::type ta;
     BLoadW<X3 ? 3 : 1> tb;
     ta.init(c, m0, tid);
     ta.load(c, rx, kbeg, kend, tid);
@@ -341,13 +476,13 @@ int fill_conv(const char *what, const ConvGeom &g, int precision, BConv &c)
 
 int64_t conv_workspace(const BConv &c) { return c.splits > 1 ? (int64_t)c.splits * c.M * c.co * 4 : 0; }
 
-template <bool X3, bool NCHW, int EPI>
+template <bool X3, int AM, int EPI>
 void launch_conv(hipStream_t s, const BConv &c)
 {
     static DeviceOnce once;
-    allow_dynamic_lds(backbone_conv_kernel<X3, NCHW, EPI>, once, BCfg<X3>::kLds);
+    allow_dynamic_lds(backbone_conv_kernel<X3, AM, EPI>, once, BCfg<X3>::kLds);
     const dim3 grid((unsigned)((c.M + kBM - 1) / kBM), (unsigned)((c.co + kBN - 1) / kBN), (unsigned)c.splits);
-    hipLaunchKernelGGL((backbone_conv_kernel<X3, NCHW, EPI>), grid, dim3(kBThreads), BCfg<X3>::kLds, s, c);
+    hipLaunchKernelGGL((backbone_conv_kernel<X3, AM, EPI>), grid, dim3(kBThreads), BCfg<X3>::kLds, s, c);
     if (c.splits > 1) {
         const int64_t total = (int64_t)c.M * c.co;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);

@@ -250,10 +250,13 @@ class HipModule(nn.Module):
         ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=device)
         _hip.launch(c_prefix + "_run", lib, device, arr, len(ops), precision, ws.data_ptr(), ws_bytes, what=f"{who} (run)")
 
-    def _pack(self, w32: Tensor, norm: Sequence[Tensor], eps: float, layout: int) -> Tuple[Tensor, Tensor]:
+    def _pack(self, w32: Tensor, norm: Sequence[Tensor], eps: float, layout: int, precision: Optional[int] = None
+              ) -> Tuple[Tensor, Tensor]:
         """``sdetr_backbone_pack`` of the fp32 conv weight ``w32`` ``[out, in, k, k]`` and the fp32 batch-norm vectors
-        ``norm`` (weight, bias, running mean, running variance): ``(packed weight, folded bias [out])``."""
-        lib, precision, (co, ci, k) = self._lib(), self._precision(), w32.shape[:3]
+        ``norm`` (weight, bias, running mean, running variance): ``(packed weight, folded bias [out])``.  ``precision``:
+        the module's own unless given (0: the three exact planes whatever the compute dtype)."""
+        lib, (co, ci, k) = self._lib(), w32.shape[:3]
+        precision = self._precision() if precision is None else precision
         packed = torch.empty(lib.sdetr_backbone_packed_bytes(co, ci, k, precision) // 2, dtype=torch.int16, device=w32.device)
         bias = torch.empty(co, dtype=torch.float32, device=w32.device)
         _hip.launch("sdetr_backbone_pack", lib, w32.device, w32.data_ptr(), *[t.data_ptr() for t in norm], eps, co, ci, k,
